@@ -1,6 +1,7 @@
 """bench.py -- SE3DS hot-path throughput on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W [--workload gan_step|warp]
+  python bench.py --gpus N --steps K --warmup W [--workload gan_step|warp] [--full]
+                 [--dump-outputs DIR]
 
 Prints ONE JSON line on rank 0 (contract in the task statement).  With --gpus N > 1 and no
 torchrun environment, this process only LAUNCHES `python -m torch.distributed.run
@@ -12,8 +13,14 @@ output: one rank per GPU over RCCL, as the reference picks its strategy from the
             metric = panoramas/sec.  Data-parallel over ranks (weak scaling).
   warp      1024x2048 equirect: 2 source views unprojected, 1 target rendered per step
             (SURVEY 8d, cfg5).  Replicas only.
-The CPU baseline leg times the oracle (oracle/, a restatement -- TF cannot run here) on a
-bounded sample on the host cores; it is a reported baseline, never the thing measured.
+A plain run sets up, warms up, times the steps and prints the headline.  --full adds everything
+else the line can carry (the rooflines and per-kernel timings, which launch work of their own, the
+gan_step line's extra measurements, the multi-rank collective figures and the CPU baseline); it
+is what the --no-* switches act on.  The CPU baseline leg times the oracle (oracle/, a
+restatement -- TF cannot run here) on a bounded sample on the host cores; it is a reported
+baseline, never the thing measured.  --dump-outputs DIR writes, after the timed steps, what the
+last one computed (.npy, float32 / float64); the inputs are seeded, so two builds can be compared
+output for output.
 """
 import argparse
 import json
@@ -214,6 +221,23 @@ def bench_warp(args, rank, world, dev):
     step()
   _barrier(world)
   dt = _max_over_ranks(time.perf_counter() - t0, world, dev)
+  if args.dump_outputs and rank == 0:
+    # the frame the last timed step rendered (depth, features, mask: 40 MB at 1024 x 2048)
+    torch.cuda.synchronize()
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    for name, t in zip(('depth', 'feats', 'mask'), frame):
+      np.save(os.path.join(args.dump_outputs, name + '.npy'), t.float().cpu().numpy())
+  out = {
+      'metric': 'panoramas/sec (2-view unproject + 1 target render, 1024x2048 equirect)',
+      'value': world * args.steps / dt, 'unit': 'panoramas/sec', 'n_gpus': world,
+      'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': 1e3 * dt / args.steps,
+      'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32',
+      'data': 'synthetic',
+      'config': {'workload': f'warp cfg5 {h}x{w} V={views} (replicas only)' +
+                             ('' if args.warp_depth == 'random' else f', {args.warp_depth} depth')},
+  }
+  if not args.full:
+    return out
 
   # dominant kernel chain = project+splat on a resident memory: HIP events on the launch stream
   step()
@@ -283,14 +307,7 @@ def bench_warp(args, rank, world, dev):
   traffic, traffic_detail = (None, None)
   if (h, views, args.warp_depth) == (1024, 2, 'random'):
     traffic, traffic_detail = _pmc_traffic('r06_warp_pmc.json', ('splat_sort',))
-  out = {
-      'metric': 'panoramas/sec (2-view unproject + 1 target render, 1024x2048 equirect)',
-      'value': world * args.steps / dt, 'unit': 'panoramas/sec', 'n_gpus': world,
-      'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': 1e3 * dt / args.steps,
-      'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32',
-      'data': 'synthetic',
-      'config': {'workload': f'warp cfg5 {h}x{w} V={views} (replicas only)' +
-                             ('' if args.warp_depth == 'random' else f', {args.warp_depth} depth')},
+  out.update({
       'roofline': {'bound': 'hbm', 'kernel': 'project+splat (splat_sort_kernel: pack + sort each chunk by target row; '
                              'splat_sort_resolve_kernel: gather, z-min, features, outputs, sink)',
                    'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
@@ -311,7 +328,7 @@ def bench_warp(args, rank, world, dev):
                    # point) and the host's share: wall per step through the Python API over that
                    'device_ms_per_step': dev_step_ms,
                    'step_over_kernels': (1e3 * dt / args.steps) / dev_step_ms},
-  }
+  })
   if rank == 0 and world == 1 and not args.no_cpu_baseline:
     out['cpu_baseline'] = cpu_baseline_warp(panos, target, h, w)
   return out
@@ -367,6 +384,12 @@ def main():
   ap.add_argument('--batch', type=int, default=0, help='per-GPU batch for gan_step (0 = auto)')
   ap.add_argument('--image-size', type=int, default=512)
   ap.add_argument('--dtype', default='bf16', choices=['bf16', 'f32'])
+  ap.add_argument('--full', action='store_true',
+                  help='everything beyond the headline: rooflines and per-kernel timings, the CPU baseline, '
+                       'the extra gan_step measurements (shipped schedule, batch_max, fp32, warp) and, with '
+                       'several ranks, the collective figures')
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                  help='after the timed steps, write what the last one computed as DIR/<name>.npy')
   ap.add_argument('--no-cpu-baseline', action='store_true')
   ap.add_argument('--no-batch-max', action='store_true',
                   help='gan_step: skip the extra large-batch measurement (batch_max) on the default line')
@@ -384,21 +407,21 @@ def main():
     raise SystemExit(f'bench.py: --gpus {args.gpus} but WORLD_SIZE={world}: launch with '
                      f'--nproc-per-node {args.gpus} (or without torchrun: bench.py spawns the ranks)')
   dev = torch.device('cuda', local)
-  preflight = _collective_preflight(rank, world, dev) if world > 1 else None
+  preflight = _collective_preflight(rank, world, dev) if world > 1 and args.full else None
   workload = args.workload
   if workload is None:
     workload = 'gan_step' if os.path.exists(os.path.join(ROOT, 'se3ds_amd', 'bench_step.py')) \
         else 'warp'
   out = bench_warp(args, rank, world, dev) if workload == 'warp' else \
       bench_gan_step(args, rank, world, dev)
-  if workload == 'gan_step' and world == 1 and not args.no_warp:
+  if workload == 'gan_step' and world == 1 and args.full and not args.no_warp:
     # the second half of the hot path, driver-observed on the default line: cfg5 warp
     # (1024x2048, 2 views) throughput and the HBM roofline of its project+splat chain
     import gc
     gc.collect()
     torch.cuda.empty_cache()
     wargs = argparse.Namespace(**vars(args))
-    wargs.steps, wargs.warmup, wargs.no_cpu_baseline = 50, 5, True
+    wargs.steps, wargs.warmup, wargs.no_cpu_baseline, wargs.dump_outputs = 50, 5, True, None
     w = bench_warp(wargs, rank, world, dev)
     out['warp'] = {k: w[k] for k in ('metric', 'value', 'unit', 'ms_per_step', 'config', 'roofline')}
     # ... and at north_star's stated size, 512 x 1024 (2 views -> 1 target)

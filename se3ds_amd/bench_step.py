@@ -80,6 +80,24 @@ def run(args, rank, world, dev, barrier, max_over_ranks):
   barrier(world)
   dt = max_over_ranks(time.perf_counter() - t0, world, dev)
   ms = 1e3 * dt / args.steps
+  if getattr(args, 'dump_outputs', None) and rank == 0:
+    dump_outputs(gan, args.dump_outputs)
+  out = {
+      'metric': 'panoramas/sec (G+D train step) at 512x1024 RGB-D' if h == 512 else
+                f'panoramas/sec (G+D train step) at {h}x{2 * h} RGB-D',
+      'value': world * n * args.steps / dt, 'unit': 'panoramas/sec', 'n_gpus': world,
+      'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': ms, 'higher_is_better': True,
+      'scaling': 'weak', 'vs_baseline': None, 'dtype': args.dtype, 'data': 'synthetic',
+      'config': {'workload': f'configs/highres {h}x{2 * h} full GAN step train_g_d (G+D+hinge+'
+                             f'depth+wc losses, clip, Adam, EMA), ResNet-101 gen_dims 128, '
+                             f'per-GPU batch {n}, d_step_per_g_step 1',
+                 'per_gpu_batch': n, 'global_batch': n * world, 'parallelism': f'dp{world}'},
+  }
+  if not getattr(args, 'full', False):
+    # a plain run ends here: the headline and what the timed steps themselves left behind
+    out['losses'] = _losses(gan)
+    out['hbm_gib_peak'] = torch.cuda.max_memory_allocated(dev) / 2**30
+    return out
 
   # ---- roofline of the dominant kernel family (implicit-GEMM convolutions): one extra,
   # instrumented step with HIP events around every conv launch on the launch stream
@@ -102,7 +120,6 @@ def run(args, rank, world, dev, barrier, max_over_ranks):
       print(f'SHAPE {ms_:8.2f} ms {fl / max(ms_, 1e-9) / 1e9:7.0f} TF/s x{cnt:3d} {kind:6s} {tag}')
   peak = BF16_PEAK_TFLOPS if args.dtype == 'bf16' else F32_PEAK_TFLOPS
   achieved = summ['flops'] / (summ['ms'] * 1e-3) / 1e12 if summ['ms'] > 0 else 0.0
-  m = gan._save_metrics_to_dict()
   # HBM traffic of the dominant kernel (3x3 1024->1024 @32x64 forward, 35 % of the conv time with
   # its data-gradient twin) from the tracked PMC summary; the family is MFMA-bound, the figure
   # shows that no kernel re-reads its operands from HBM (algorithmic: 52 MB in, 33.5 MB out)
@@ -114,16 +131,7 @@ def run(args, rank, world, dev, barrier, max_over_ranks):
     if traffic_detail is not None:
       traffic_detail['kernel'] = 'igemm_halo_kernel<0, 256, 2> (3x3 1024->1024 @32x64, batch 8)'
       traffic_detail['algorithmic_mb'] = 52.4 + 33.6
-  out = {
-      'metric': 'panoramas/sec (G+D train step) at 512x1024 RGB-D' if h == 512 else
-                f'panoramas/sec (G+D train step) at {h}x{2 * h} RGB-D',
-      'value': world * n * args.steps / dt, 'unit': 'panoramas/sec', 'n_gpus': world,
-      'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': ms, 'higher_is_better': True,
-      'scaling': 'weak', 'vs_baseline': None, 'dtype': args.dtype, 'data': 'synthetic',
-      'config': {'workload': f'configs/highres {h}x{2 * h} full GAN step train_g_d (G+D+hinge+'
-                             f'depth+wc losses, clip, Adam, EMA), ResNet-101 gen_dims 128, '
-                             f'per-GPU batch {n}, d_step_per_g_step 1',
-                 'per_gpu_batch': n, 'global_batch': n * world, 'parallelism': f'dp{world}'},
+  out.update({
       'roofline': {'bound': 'mfma', 'kernel': 'implicit-GEMM convolutions: igemm_halo / igemm_big / '
                    'igemm_glds + wgrad_taps / wgrad_glds (every conv fwd, dgrad and wgrad call of '
                    'one step)', 'achieved': achieved, 'peak': peak, 'unit': 'TFLOP/s',
@@ -137,10 +145,9 @@ def run(args, rank, world, dev, barrier, max_over_ranks):
                    'avg_launch_ms': summ['ms'] / max(summ['launches'], 1),
                    'conv_ms_per_step': summ['ms'], 'conv_tflop_per_step': summ['flops'] / 1e12,
                    'by_kind': summ['by_kind']},
-      'losses': {k: float(v) for k, v in m.items() if k in (
-          'gen/gen_gan_loss', 'dis/disc_loss', 'gen/depth_loss', 'gen/wc_loss')},
+      'losses': _losses(gan),
       'hbm_gib_peak': torch.cuda.max_memory_allocated(dev) / 2**30,
-  }
+  })
   if world > 1:
     # one more step with the collective log on: what a rank sends per step (the scaling curve's
     # explanation: ~390 latency-bound SyncBN sums + 4.46 GB of gradient buckets per step)
@@ -191,6 +198,42 @@ def run(args, rank, world, dev, barrier, max_over_ranks):
   if rank == 0 and world == 1 and not args.no_cpu_baseline:
     out['cpu_baseline'] = cpu_baseline(args, gan, summ['flops'] / 1e12 / n)
   return out
+
+
+LOSS_KEYS = ('gen/gen_gan_loss', 'dis/disc_loss', 'gen/depth_loss', 'gen/wc_loss')
+
+
+def _losses(gan):
+  """Mean losses over every step taken so far (raises on a NaN, as the trainer's own log does)."""
+  m = gan._save_metrics_to_dict()
+  return {k: float(v) for k, v in m.items() if k in LOSS_KEYS}
+
+
+def dump_outputs(gan, out_dir, sample=1 << 20):
+  """What the last `train_g_d` handed its caller, as .npy files under `out_dir`: that step's losses
+  and gradient norms (float64, one file per metric) and the updated parameters -- the trainable and
+  the state arena of the generator, the discriminator and the EMA generator, each a fixed sample of
+  at most `sample` elements (float32; indices drawn once from a seeded generator, sorted)."""
+  import numpy as np
+  torch.cuda.synchronize()
+  os.makedirs(out_dir, exist_ok=True)
+  for k, metric in gan.metrics.items():
+    v = metric._vals[-1] if metric._vals else 0.0
+    v = v() if callable(v) else v
+    if isinstance(v, torch.Tensor):
+      v = v.detach().double().cpu().numpy().reshape(-1)
+    np.save(os.path.join(out_dir, k.replace('/', '_') + '.npy'), np.asarray(v, np.float64).reshape(-1))
+  for name, model in (('generator', gan.generator), ('discriminator', gan.discriminator),
+                      ('ema_generator', gan.ema_generator)):
+    for part in ('theta', 'state'):
+      arena = getattr(model.store, part)
+      if arena is None or arena.numel() == 0:
+        continue
+      flat = arena.detach().reshape(-1)
+      if flat.numel() > sample:
+        idx = np.sort(np.random.default_rng(0).integers(0, flat.numel(), sample))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+      np.save(os.path.join(out_dir, f'{name}_{part}.npy'), flat.float().cpu().numpy())
 
 
 def shipped_schedule(gan, n, h, dev, rank, steps=3):

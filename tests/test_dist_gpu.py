@@ -94,7 +94,7 @@ def test_bench_gpus_2_launches_two_ranks_on_one_gpu():
   On a 1-GPU box the ranks share cuda:0 and rendezvous over gloo (SE3DS_BENCH_BACKEND); the warp
   workload is replicas-only, so this exercises exactly the launcher / barrier / max-over-ranks
   plumbing of the multi-GPU bench."""
-  out = _run_bench(['--gpus', '2', '--workload', 'warp', '--warp-height', '64', '--steps', '3',
+  out = _run_bench(['--full', '--gpus', '2', '--workload', 'warp', '--warp-height', '64', '--steps', '3',
                     '--warmup', '1', '--no-cpu-baseline'], dict(SE3DS_BENCH_BACKEND='gloo'))
   assert out['n_gpus'] == 2 and out['steps'] == 3 and out['value'] > 0
   assert out['scaling'] == 'weak' and out['config']['workload'].startswith('warp')
@@ -110,7 +110,7 @@ def test_bench_gan_step_two_gloo_ranks_on_one_gpu():
   gloo (small model: the figure says nothing about throughput) -- the launcher, the data-parallel
   strategy with branch streams and side-stream gradient hand-over, barrier + max-over-ranks timing
   and the line's n_gpus / global_batch / backend fields."""
-  out = _run_bench(['--gpus', '2', '--steps', '2', '--warmup', '1', '--batch', '1', '--image-size',
+  out = _run_bench(['--full', '--gpus', '2', '--steps', '2', '--warmup', '1', '--batch', '1', '--image-size',
                     '128', '--no-cpu-baseline', '--no-warp', '--no-shipped', '--no-batch-max'],
                    dict(SE3DS_BENCH_BACKEND='gloo'), timeout=900)
   assert out['n_gpus'] == 2 and out['config']['global_batch'] == 2 and out['backend'] == 'gloo'

@@ -1,14 +1,15 @@
 # per-shape conv times inside the instrumented step (SE3DS_BENCH_SHAPES=1) under env variants
-# usage: shapes_ab.sh TAG ENV=v [ENV=v ...]   -> gpurun_out/shapes_TAG_<i>_<rep>.log
+# usage: shapes_ab.sh TAG ENV=v [ENV=v ...]   -> $OUT/shapes_TAG_<i>_<rep>.log
 cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
-mkdir -p gpurun_out
+OUT=${SE3DS_OUT:-out}
+mkdir -p "$OUT"
 tag=$1; shift
 for rep in 1 2; do
   i=0
   for v in "$@"; do
-    env $v SE3DS_BENCH_SHAPES=all timeout 600 python bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-batch-max --no-warp --no-shipped --no-fp32 2>/dev/null > gpurun_out/shapes_${tag}_${i}_${rep}.log
-    python - gpurun_out/shapes_${tag}_${i}_${rep}.log "$v rep$rep" <<'PY'
+    env $v SE3DS_BENCH_SHAPES=all timeout 600 python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-batch-max --no-warp --no-shipped --no-fp32 2>/dev/null > $OUT/shapes_${tag}_${i}_${rep}.log
+    python - $OUT/shapes_${tag}_${i}_${rep}.log "$v rep$rep" <<'PY'
 import sys, json
 lines = open(sys.argv[1]).read().splitlines()
 sh = [l.split() for l in lines if l.startswith('SHAPE')]
