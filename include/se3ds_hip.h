@@ -652,6 +652,36 @@ int se3ds_input_transform(const uint8_t* image, const uint8_t* proj_image, const
                           float* o_proj_depth, float* o_depth, float* o_blurred, int32_t* o_seg,
                           void* stream);
 
+/* ======================================================================================
+ * Inception-v3 evaluator -- utils/inception_utils.py, utils/eval_metric.py EvalMetric
+ * (reference utils/inception_utils.py, utils/eval_metric.py:66-343).  csrc/inception.hip.
+ * ====================================================================================== */
+/* (N,H,W,3) fp32 frames in [0,1] -> network input (N,oh,ow,3) F32 / BF16, one gather:
+ * indoor_datasets.augment (roll_flip: device int32 [N][2] = (roll, flip) per image, or NULL for
+ * none), crop_pano(resize_to_original=False) (crop_rows = floor(H/8) rows off top and bottom),
+ * tf.image.resize bilinear (half-pixel centres, no antialias; se3ds_resize's arithmetic), then
+ * clip(x*2-1, -1, 1).  Bit-identical to that chain run op by op. */
+int se3ds_inception_preprocess(const float* frames, int n, int h, int w, const int32_t* roll_flip,
+                               int crop_rows, int oh, int ow, void* out, int out_dtype,
+                               void* stream);
+/* Keras MaxPooling2D(3, strides=2, 'valid') / AveragePooling2D(3, strides=1, 'same') (padded taps
+ * excluded from the divisor), NHWC F32 / BF16.  x is dense (n,h,w,c); y's pixels have y_c
+ * channels of which [y_c0, y_c0 + c) are written (a slice of a concatenated block output). */
+int se3ds_inception_maxpool3s2(const void* x, int dtype, int n, int h, int w, int c, void* y,
+                               int y_c, int y_c0, void* stream);
+int se3ds_inception_avgpool3s1(const void* x, int dtype, int n, int h, int w, int c, void* y,
+                               int y_c, int y_c0, void* stream);
+/* GlobalAveragePooling2D: y (n,c) fp32 = mean over the hw pixels of x (n,hw,c) F32 / BF16. */
+int se3ds_global_avg_pool(const void* x, int dtype, int n, int hw, int c, float* y, void* stream);
+/* tf.nn.softmax over each row of x (rows,c) F32 / BF16 -> y fp32. */
+int se3ds_softmax_rows(const void* x, int dtype, int64_t rows, int c, float* y, void* stream);
+/* Running binary64 moments of fp32 rows x (rows,c): *count += rows, sum[j] += sum_b x[b,j],
+ * gram[i][j] += sum_b x[b,i] x[b,j] for the 64 x 64 tiles with i-tile <= j-tile (the strictly
+ * lower tiles are not written; the matrix is symmetric).  No atomics, fixed order:
+ * bit-reproducible. */
+int se3ds_feature_moments_accumulate(const float* x, int64_t rows, int c, int64_t* count,
+                                     double* sum, double* gram, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -58,6 +58,13 @@ _SIGS = {
     'se3ds_compact_workspace_bytes': (c_sz, [c_i64]),
     'se3ds_compact_valid': (c_int, [c_p, c_p, c_int, c_int, c_i64, c_int, c_f, c_p, c_p, c_p, c_p,
                                     c_sz, c_p]),
+    'se3ds_inception_preprocess': (c_int, [c_p, c_int, c_int, c_int, c_p, c_int, c_int, c_int, c_p,
+                                           c_int, c_p]),
+    'se3ds_inception_maxpool3s2': (c_int, [c_p] + [c_int] * 5 + [c_p, c_int, c_int, c_p]),
+    'se3ds_inception_avgpool3s1': (c_int, [c_p] + [c_int] * 5 + [c_p, c_int, c_int, c_p]),
+    'se3ds_global_avg_pool': (c_int, [c_p, c_int, c_int, c_int, c_int, c_p, c_p]),
+    'se3ds_softmax_rows': (c_int, [c_p, c_int, c_i64, c_int, c_p, c_p]),
+    'se3ds_feature_moments_accumulate': (c_int, [c_p, c_i64, c_int, c_p, c_p, c_p, c_p]),
 }
 
 _lib = None

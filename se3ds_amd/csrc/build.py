@@ -19,6 +19,7 @@ COMMON = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wall', '-Wno-
 PER_FILE = {
     'geom.hip': ['-ffp-contract=off'],
     'input.hip': ['-ffp-contract=off'],
+    'inception.hip': ['-ffp-contract=off'],
 }
 
 

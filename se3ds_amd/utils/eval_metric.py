@@ -4,14 +4,23 @@ utils/eval_metric.py `_get_generated_pool.step_fn` (:144-239) and in trainers/ga
 generator in inference mode, quantise, unproject the (ground-truth first, then generated) frame and
 append it to the memory -- as ONE on-device pipeline.  Every arithmetic step runs in
 libse3ds_hip.so; the memory lives in preallocated HBM buffers (PointCloudMemory), so no frame ever
-copies it.  The Inception / FID half of the reference's evaluator is out of scope."""
-from typing import Callable, Dict, List, NamedTuple, Optional
+copies it.
 
+EvalMetric is the other half of the reference's evaluator (:66-343): the FID per frame index of the
+roll-out against real frames, averaged over `avg_num` repeats, and the depth RMSE.  Real and
+generated frames go through the augment + crop + resize gather and Inception-v3 on the device
+(utils/inception_utils.py); their 2048-d pools are reduced there into binary64 moments
+(FeatureMoments), so only the mean and covariance reach the host for the Frechet distance."""
+from typing import Callable, Dict, Iterator, List, NamedTuple, Optional
+
+import numpy as np
 import torch
 
 from se3ds_amd import _lib
 from se3ds_amd import constants
+from se3ds_amd.datasets import indoor_datasets
 from se3ds_amd.models.models import _quantize
+from se3ds_amd.utils import inception_utils
 from se3ds_amd.utils import pano_utils
 from se3ds_amd.utils import point_cloud_utils
 from se3ds_amd.utils.point_cloud_utils import PointCloudMemory
@@ -105,3 +114,97 @@ def generated_rollout(generator_fn: Callable, inputs: Dict[str, torch.Tensor], e
     out.proj_depth.append(pred_depth[..., None])
   point_cloud_utils.check_promise(memory.device)   # (the roll-out's results are read next)
   return out
+
+
+class EvalMetric:
+  """FID (and depth RMSE) of a generator's roll-outs (reference utils/eval_metric.py:66-343).
+
+  ds: an iterator of the batch dicts generated_rollout takes (image (N,T,H,W,3) fp32 [0,1], depth,
+  position, depth_scale; an `original_image` entry, if present, supplies the real frames as in the
+  reference).  eval_num rows per frame index enter each statistic; `inception` defaults to
+  inception_utils.inception_model() (gin-configurable).  Augment draws come from a NumPy generator
+  seeded with `seed`.  strategy: only None (a single device) is supported; per-rank
+  FeatureMoments can be merged by the caller.  keep_pools: also keep the host copies of the pools
+  of the real set and of the last repeat (tests)."""
+
+  def __init__(self, ds: Iterator, eval_num: int, batch_size: int, strategy=None, avg_num: int = 3,
+               num_splits: int = 1, eval_seq_len: int = 5,
+               inception: Optional[inception_utils.InceptionV3] = None, seed: int = 0,
+               keep_pools: bool = False) -> None:
+    if strategy is not None:
+      raise NotImplementedError('EvalMetric runs on one device; merge FeatureMoments across ranks')
+    self.ds = ds
+    self.eval_num = eval_num
+    self.batch_size = batch_size
+    self.strategy = strategy
+    self.avg_num = avg_num
+    self.num_splits = num_splits
+    self.eval_seq_len = eval_seq_len
+    self._inception_model = inception if inception is not None else inception_utils.inception_model()
+    self._rng = np.random.default_rng(seed)
+    self.keep_pools = keep_pools
+    self.real_pools = None
+    self.generated_pools = None
+    self.fid_list = None
+    # Real statistics once (:107-131, 269-286)
+    def real_fn(batch):
+      image = batch.get('original_image', batch['image'])
+      return {i: image[:, i] for i in range(1, eval_seq_len)}, None
+
+    self._real = self._moments(real_fn, 'real_pools')
+
+  def _pools(self, frames: torch.Tensor) -> torch.Tensor:
+    """augment -> crop_pano(resize_to_original=False) -> get_inception (:114-131, 240-251)."""
+    n, _, w, _ = frames.shape
+    rf = np.array([indoor_datasets.draw_augment(self._rng, w) for _ in range(n)], np.int32)
+    x = inception_utils.preprocess(frames, roll_flip=rf, crop=True, dtype=self._inception_model.dtype)
+    pools, _ = self._inception_model(x)
+    return pools
+
+  def _moments(self, frames_fn, keep_attr, rmse=None):
+    """Per frame index 1..T-1: FeatureMoments over the first eval_num rows of
+    (eval_num // batch_size + 1) batches (:269-315)."""
+    stats = {i: inception_utils.FeatureMoments(device=self._inception_model.device)
+             for i in range(1, self.eval_seq_len)}
+    kept = {i: [] for i in stats}
+    rmse_rows = {i: [] for i in stats}
+    left = self.eval_num
+    for _ in range(self.eval_num // self.batch_size + 1):
+      batch = next(self.ds)
+      frames, depth_rmse_k = frames_fn(batch)
+      if left <= 0:
+        continue   # (the reference draws the batch and drops it)
+      for i in stats:
+        pools = self._pools(frames[i].contiguous())[:left]
+        stats[i].update(pools)
+        if self.keep_pools:
+          kept[i].append(pools.cpu().numpy())
+        if depth_rmse_k is not None:
+          rmse_rows[i].append(depth_rmse_k[i][:left].cpu().numpy())
+      left -= min(left, frames[1].shape[0])
+    if self.keep_pools:
+      setattr(self, keep_attr, {i: np.concatenate(v) for i, v in kept.items()})
+    if rmse is not None:
+      rmse.update({i: np.concatenate(v) for i, v in rmse_rows.items()})
+    return stats
+
+  def calculate_fid_score(self, generator_fn: Callable):
+    """(fid, fid_std, rmse): dicts keyed by frame index 1..T-1 (:317-343)."""
+    def frames_fn(batch):
+      out = generated_rollout(generator_fn, batch, self.eval_seq_len)
+      return ({i: out.generated[i] for i in range(1, self.eval_seq_len)},
+              {i: out.depth_rmse[i] for i in range(1, self.eval_seq_len)})
+
+    fid_list = {i: [] for i in range(1, self.eval_seq_len)}
+    rmse_list = {i: [] for i in range(1, self.eval_seq_len)}
+    for _ in range(self.avg_num):
+      rmse_total = {}
+      gen = self._moments(frames_fn, 'generated_pools', rmse=rmse_total)
+      for i in fid_list:
+        fid_list[i].append(gen[i].fid(self._real[i]))
+        rmse_list[i].append(np.mean(rmse_total[i]))
+    self.fid_list = fid_list
+    fid = {k: np.mean(v) for k, v in fid_list.items()}
+    fid_std = {k: np.std(v) for k, v in fid_list.items()}
+    rmse = {k: np.mean(v) for k, v in rmse_list.items()}
+    return fid, fid_std, rmse
