@@ -253,11 +253,6 @@ class Ctx:
     # {tag: torch.cuda.Stream}, None = everything on the current stream.  Ops record the branch
     # they ran in; backward() replays each branch's closures on its stream (see branch()).
     self.streams = None
-    self.stream_phases = ('fwd', 'bwd')   # debugging: restrict the branch streams to one pass
-    # Weight gradients leave the backward pass's dependency chain (dgrad -> norm backward ->
-    # dgrad ...): with a stream here, every conv layer's wgrad goes to it behind an event on dy,
-    # and MFMA-bound wgrads run under the HBM-bound normalisation kernels of the chain.
-    self.wgrad_stream = None
     # Deferred split reductions of the weight gradients (round 4): a list collects one row per conv
     # layer [slabs, splits, n / 4, destination]; flush_wgrad_reduces() runs them as ONE launch (the
     # trainer: per module, on the optimiser's side stream).  None: every layer reduces right away.
@@ -325,16 +320,10 @@ class Ctx:
     if self.world > 1 and len(fns) == 2:
       return _run_paired(self, fns)
     out = {}
-    keep = self.streams
-    if 'fwd' not in self.stream_phases:
-      self.streams = None
-    try:
-      for tag, fn in fns.items():
-        with self.branch(tag):
-          out[tag] = fn()
-      self.join()
-    finally:
-      self.streams = keep
+    for tag, fn in fns.items():
+      with self.branch(tag):
+        out[tag] = fn()
+    self.join()
     return out
 
   def branch(self, tag):
@@ -353,34 +342,11 @@ class Ctx:
         main.wait_stream(self.streams[tag])
       self._forked.clear()
 
-  def on_wgrad_stream(self, *reads):
-    """with ctx.on_wgrad_stream(dy, ...): a weight-gradient launch.  Returns a context manager
-    that switches to the wgrad stream behind an event on the current stream; `reads` are tensors
-    of the current stream's allocator that the launch reads (they may be freed by the caller
-    right away: record_stream keeps their memory until the wgrad stream has passed)."""
-    return _WgradScope(self, reads)
-
-  def wgrad_event(self):
-    """Event behind everything issued to the wgrad stream so far (None without one)."""
-    if self.wgrad_stream is None:
-      return None
-    ev = torch.cuda.Event()
-    ev.record(self.wgrad_stream)
-    return ev
-
   def backward(self):
     tape, self.tape = self.tape, []
     if self.world > 1:
       tape = _merge_paired(tape)
-    keep = self.streams
-    if 'bwd' not in self.stream_phases:
-      self.streams = None
-    try:
-      self._replay(tape)
-    finally:
-      self.streams = keep
-    if self.wgrad_stream is not None:   # every gradient is final when backward() returns
-      torch.cuda.current_stream(self.device).wait_stream(self.wgrad_stream)
+    self._replay(tape)
 
   def _replay(self, tape):
     cur, scope = 0, None
@@ -479,28 +445,6 @@ class Ctx:
     cont()
 
 
-class _WgradScope:
-  def __init__(self, ctx, reads):
-    self.ctx, self.reads, self.scope = ctx, reads, None
-
-  def __enter__(self):
-    ws = self.ctx.wgrad_stream
-    if ws is not None:
-      ev = torch.cuda.Event()
-      ev.record()
-      ws.wait_event(ev)
-      for t in self.reads:
-        if t is not None:
-          t.record_stream(ws)
-      self.scope = torch.cuda.stream(ws)
-      self.scope.__enter__()
-    return self
-
-  def __exit__(self, *a):
-    if self.scope is not None:
-      self.scope.__exit__(*a)
-
-
 class _Branch:
   def __init__(self, ctx, tag):
     self.ctx, self.tag, self.scope, self.prev = ctx, tag, None, 0
@@ -565,10 +509,6 @@ def _run_paired(ctx, fns):
   on_gpu = ctx.device.type == 'cuda'
   dev, stream = ctx.device, (torch.cuda.current_stream(ctx.device) if on_gpu else None)
 
-  keep = ctx.streams
-  if 'fwd' not in ctx.stream_phases:
-    ctx.streams = None   # (debugging switch: the forward pass on one stream, as run_branches does)
-
   def work(tag):
     try:
       if on_gpu:
@@ -591,7 +531,6 @@ def _run_paired(ctx, fns):
     th.join()
   finally:
     ctx.pair = None
-    ctx.streams = keep
   if err:
     real = [e for e in err if not isinstance(e, threading.BrokenBarrierError)]
     raise (real or err)[0]
@@ -657,50 +596,6 @@ def _grad_mark(var):
 
 
 _WS = {}
-
-
-def make_stream(device, role: str):
-  """A side stream of the step's schedule (`role`: 'branch1' / 'branch2' = the two decoders,
-  'optimizer', 'discriminator', 'wgrad').  SE3DS_CU_MASK (round 6, VERDICT r5 item 4 -- the measured
-  attempt at CO-RUNNING the HBM-bound kernels under the convolutions: an 8-wave conv workgroup at 256
-  registers per lane owns a CU's whole register file and 150 KB of its LDS, so a kernel of another
-  stream only ever gets CUs between conv workgroups; a CU mask gives it CUs of its own) selects a
-  plan of `hipExtStreamCreateWithCUMask` masks:
-    halves     branch1 on CUs 0-127, branch2 on 128-255 (contiguous in the mask's enumeration)
-    alternate  branch1 on the even, branch2 on the odd CUs
-    opt32 / opt64   only the optimizer stream is confined, to the last 32 / 64 CUs
-  Unset (the default, and what every measurement outside tools/probes/cu_mask_ab.sh runs): plain
-  streams.  DESIGN.md section 3.4 has the A/B."""
-  plan = os.environ.get('SE3DS_CU_MASK')
-  dev = torch.device(device)
-  mask = None
-  if plan and dev.type == 'cuda':
-    ncu = torch.cuda.get_device_properties(dev).multi_processor_count
-    bits = None
-    if plan == 'halves' and role in ('branch1', 'branch2'):
-      bits = [(i < ncu // 2) == (role == 'branch1') for i in range(ncu)]
-    elif plan == 'alternate' and role in ('branch1', 'branch2'):
-      bits = [(i % 2 == 0) == (role == 'branch1') for i in range(ncu)]
-    elif plan in ('opt32', 'opt64') and role == 'optimizer':
-      k = int(plan[3:])
-      bits = [i >= ncu - k for i in range(ncu)]
-    if bits is not None:
-      words = (ncu + 31) // 32
-      mask = [0] * words
-      for i, b in enumerate(bits):
-        if b:
-          mask[i // 32] |= 1 << (i % 32)
-  if mask is None:
-    return torch.cuda.Stream(dev)
-  import ctypes
-  hip = ctypes.CDLL('libamdhip64.so')
-  st = ctypes.c_void_p()
-  arr = (ctypes.c_uint32 * len(mask))(*mask)
-  with torch.cuda.device(dev):
-    rc = hip.hipExtStreamCreateWithCUMask(ctypes.byref(st), ctypes.c_uint32(len(mask)), arr)
-  if rc != 0:
-    raise _lib.Se3dsHipError(f'hipExtStreamCreateWithCUMask failed ({rc}) for SE3DS_CU_MASK={plan}')
-  return torch.cuda.ExternalStream(st.value, device=dev)
 
 
 class ConvProfiler:
@@ -1274,23 +1169,22 @@ def conv2d(ctx: Ctx, x: Var, layer: ConvLayer, pad=0, wrap=False, mask=None, act
         gk = st.grad_views[layer.name + '/kernel']
         thin_out = (layer.cout <= 16 and cin > 16 and s == 1 and ho == h and wo == w and
                     pt == pl and not wrap and not partial)
-        with ctx.on_wgrad_stream(dys, row_scale):   # (scratch below is per stream)
-          if thin_out:
-            # 128->3 / 128->1 output convs: role-swapped weight gradient (x streamed once)
-            wsz = L.se3ds_conv2d_wgrad_swapped_workspace_bytes(n, h, w, cin, layer.cout, k)
-            ws = _global_ws(ctx.device, 'wgrad', wsz)
-            with _Timed('wgrad', flops, tag):
-              _chk(L.se3ds_conv2d_wgrad_swapped(xd.data_ptr(), dys.data_ptr(), gk.data_ptr(),
-                                                ctx.code, n, h, w, cin, layer.cout, k, pt, 0,
-                                                ws.data_ptr(), ws.numel(), _lib.stream()),
-                   'se3ds_conv2d_wgrad_swapped')
-          else:
-            wsz = L.se3ds_conv2d_wgrad_workspace_bytes(n, ho, wo, cin, layer.cout, k, k)
-            with _Timed('wgrad', flops, tag):
-              _wgrad(ctx, layer, (xd.data_ptr(), dys.data_ptr(), gk.data_ptr(), ctx.code, n, h,
-                                  w, cin, ho, wo, layer.cout, k, k, s, pt, pl,
-                                  1 if wrap else 0, _lib.ptr(in_mask),
-                                  1 if ctx.binary_masks else 0, _lib.ptr(row_scale)), wsz)
+        if thin_out:
+          # 128->3 / 128->1 output convs: role-swapped weight gradient (x streamed once)
+          wsz = L.se3ds_conv2d_wgrad_swapped_workspace_bytes(n, h, w, cin, layer.cout, k)
+          ws = _global_ws(ctx.device, 'wgrad', wsz)
+          with _Timed('wgrad', flops, tag):
+            _chk(L.se3ds_conv2d_wgrad_swapped(xd.data_ptr(), dys.data_ptr(), gk.data_ptr(),
+                                              ctx.code, n, h, w, cin, layer.cout, k, pt, 0,
+                                              ws.data_ptr(), ws.numel(), _lib.stream()),
+                 'se3ds_conv2d_wgrad_swapped')
+        else:
+          wsz = L.se3ds_conv2d_wgrad_workspace_bytes(n, ho, wo, cin, layer.cout, k, k)
+          with _Timed('wgrad', flops, tag):
+            _wgrad(ctx, layer, (xd.data_ptr(), dys.data_ptr(), gk.data_ptr(), ctx.code, n, h,
+                                w, cin, ho, wo, layer.cout, k, k, s, pt, pl,
+                                1 if wrap else 0, _lib.ptr(in_mask),
+                                1 if ctx.binary_masks else 0, _lib.ptr(row_scale)), wsz)
       if x.requires_grad:
         prev = x.grad
         shape = (n,) + tuple(xd.shape[1:])

@@ -18,7 +18,6 @@ from se3ds_amd.models import layers
 
 # independent branches of a model on their own HIP streams (SE3DS_DUAL_STREAM=0: one stream)
 _DUAL_STREAM = os.environ.get('SE3DS_DUAL_STREAM', '1') != '0'
-_DUAL_PHASES = os.environ.get('SE3DS_DUAL_PHASES', '')   # debugging: 'fwd' or 'bwd' only
 # ... also with several replicas (opt-in until it has run over RCCL on two real GPUs)
 _DUAL_STREAM_DP = os.environ.get('SE3DS_DUAL_STREAM_DP', '0') == '1'
 
@@ -89,10 +88,8 @@ class _Model:
       # so it is opt-in, SE3DS_DUAL_STREAM_DP=1, until tests/test_dist_gpu.py's two-GPU tests have
       # passed on hardware; the default multi-replica step is the single-stream schedule)
       if getattr(self, '_branch_streams', None) is None:
-        self._branch_streams = {1: nn.make_stream(self.device, 'branch1'), 2: nn.make_stream(self.device, 'branch2')}
+        self._branch_streams = {1: torch.cuda.Stream(self.device), 2: torch.cuda.Stream(self.device)}
       ctx.streams = self._branch_streams
-      if _DUAL_PHASES:
-        ctx.stream_phases = tuple(_DUAL_PHASES.split(','))
     return ctx
 
 
@@ -353,7 +350,7 @@ class ResNetGenerator(_Model):
     # Same-box A/B: 190.9 / 191.1 vs 191.6 / 191.8 ms per step; bit-identical to the serial order
     # (tools/step_compare.py).
     sn_ev = None
-    if ctx.streams is not None and 'fwd' in ctx.stream_phases:
+    if ctx.streams is not None:
       side = ctx.streams[1]
       side.wait_stream(torch.cuda.current_stream(ctx.device))
       with torch.cuda.stream(side):

@@ -31,14 +31,6 @@ FUSED_SN_CLIP = True
 GRAD_CLIP_NORM = 5.0   # _clip_grad default, reference :27
 # one replica: per-module clip + Adam on a side stream under the backward pass (0: after it)
 SEGMENT_OPTIMIZER = os.environ.get('SE3DS_SEGMENT_OPTIMIZER', '1') != '0'
-# one replica: the discriminator's parameter-gradient pass on a side stream under the generator's
-# backward pass (train_g_d).  Bit-identical; measured 213.8 / 214.1 ms against 214.1 / 214.6 ms per
-# step on one box (-0.2 %, inside the noise) for 0.7 GB more memory: off, kept for A/B runs.
-D_OVERLAP = os.environ.get('SE3DS_D_OVERLAP', '0') != '0'
-# one replica: weight gradients on their own stream (Ctx.on_wgrad_stream).  Bit-identical, but
-# measured SLOWER (221.0 vs 213.5 ms per step, same box): two MFMA-bound kernels co-running cost
-# more than the dependency chain gains.  Off; kept for A/B runs.
-WGRAD_STREAM = os.environ.get('SE3DS_WGRAD_STREAM', '0') != '0'
 # one replica: per-tensor clip (+ spectral fix-up) inside the Adam pass -- the gradient arena is read
 # once and never rewritten (AdamState.clip_apply).  Bit-identical; 0 = the two separate passes.
 FUSED_CLIP_ADAM = os.environ.get('SE3DS_FUSED_CLIP_ADAM', '1') != '0'
@@ -157,19 +149,9 @@ class GAN(gan_manager.GANManager):
       cache[key] = nn.OperandGroup(layers, dtype, model.store.theta.device)
     return cache[key]
 
-  def _d_stream(self, dev):
-    if getattr(self, '_dis_stream', None) is None:
-      self._dis_stream = torch.cuda.Stream(dev)
-    return self._dis_stream
-
-  def _wgrad_stream(self, dev):
-    if getattr(self, '_wg_stream', None) is None:
-      self._wg_stream = torch.cuda.Stream(dev)
-    return self._wg_stream
-
   def _optimizer_stream(self, dev):
     if getattr(self, '_opt_stream', None) is None:
-      self._opt_stream = nn.make_stream(dev, 'optimizer')
+      self._opt_stream = torch.cuda.Stream(dev)
     return self._opt_stream
 
   def _grad_sync(self):
@@ -295,48 +277,26 @@ class GAN(gan_manager.GANManager):
     tape_d = ctx_d.tape
     ctx_d.tape = None
 
-    def pass1():
-      # discriminator parameter gradients (disc_tape, :244)
-      ctx_d.param_grads = True
-      ctx_d.batch_limit = None
-      self._set_input_grad(x_all, False)
-      self._backward_tape(ctx_d, tape_d, seeds_d, logits)
-      D.spectral.backward_fixup()
-
-    def pass2():
-      # gradient of the generator loss w.r.t. the fake images (gen_tape, :236).  Only the fake
-      # half of [fake; real] carries generator loss, and nothing in the discriminator couples
-      # samples (instance norm, no batch statistics): the pass runs on the first n samples of
-      # every saved activation.
-      ctx_d.param_grads = False
-      ctx_d.batch_limit = n
-      self._set_input_grad(x_all, True)
-      self._backward_tape(ctx_d, tape_d, [g[:n] for g in seeds_g], logits)
-      ctx_d.batch_limit = None
-      g = x_all.grad
-      x_all.grad = None
-      return g
-
-    side_opt = sync is None and SEGMENT_OPTIMIZER and nn.conv_profiler() is None
-    d_done = None
-    if side_opt and D_OVERLAP:
-      # One replica: the generator's backward pass only needs pass 2.  Pass 1 (the discriminator's
-      # own parameter gradients over [fake; real]) is issued behind it on a side stream and runs
-      # under the generator's backward pass; the discriminator's activations stay alive until the
-      # streams have joined (tape_d is released at the end of the step).
-      gx = pass2()
-      dstream = self._d_stream(dev)
-      dstream.wait_stream(torch.cuda.current_stream(dev))
-      with torch.cuda.stream(dstream):
-        pass1()
-        d_done = torch.cuda.Event()
-        d_done.record()
-    else:
-      pass1()
-      if sync is not None:
-        d_norm = self._sync_discriminator(sync)
-      gx = pass2()
-      del tape_d
+    # pass 1: discriminator parameter gradients (disc_tape, :244)
+    ctx_d.param_grads = True
+    ctx_d.batch_limit = None
+    self._set_input_grad(x_all, False)
+    self._backward_tape(ctx_d, tape_d, seeds_d, logits)
+    D.spectral.backward_fixup()
+    if sync is not None:
+      d_norm = self._sync_discriminator(sync)
+    # pass 2: gradient of the generator loss w.r.t. the fake images (gen_tape, :236).  Only the
+    # fake half of [fake; real] carries generator loss, and nothing in the discriminator couples
+    # samples (instance norm, no batch statistics): the pass runs on the first n samples of every
+    # saved activation.
+    ctx_d.param_grads = False
+    ctx_d.batch_limit = n
+    self._set_input_grad(x_all, True)
+    self._backward_tape(ctx_d, tape_d, [g[:n] for g in seeds_g], logits)
+    ctx_d.batch_limit = None
+    gx = x_all.grad
+    x_all.grad = None
+    del tape_d
     g_rgb = nn.slice_channels(gx[:n], 0, 3, torch.float32)
     _lib.check(L.se3ds_add(d_rgb.data_ptr(), g_rgb.data_ptr(), _lib.F32, d_rgb.numel(),
                            d_rgb.data_ptr(), _lib.stream()), 'se3ds_add')
@@ -346,17 +306,11 @@ class GAN(gan_manager.GANManager):
                              d_depth.data_ptr(), _lib.stream()), 'se3ds_add')
     # ---- generator backward
     ctx_g.param_grads = True
-    if ctx_g.streams is not None and WGRAD_STREAM and sync is None:
-      # ONE replica only: the conv layers' weight gradients leave the dgrad -> norm -> dgrad chain.
-      # (With several replicas the segment hand-over below orders the optimiser's stream behind the
-      # module's backward stream only: a wgrad stream would let clip / all-reduce read slabs and
-      # gradients whose kernels are still running.)
-      ctx_g.wgrad_stream = self._wgrad_stream(dev)
     push_rgb(d_rgb)
     push_depth(d_depth)
     # ---- clip per tensor (per replica), aggregate, apply (:238-257)
     ema_theta, ema_omd = self.ema_fused_args()   # EMA of the trainable variables rides on Adam
-    if side_opt:
+    if sync is None and SEGMENT_OPTIMIZER and nn.conv_profiler() is None:
       # (not while the bench times single convolution launches: see _Model.make_ctx)
       # One replica: a module's spectral fix-up, per-tensor clip and Adam (+ EMA) update run on a
       # SIDE STREAM as soon as the backward pass has left the module, under the rest of the
@@ -366,10 +320,8 @@ class GAN(gan_manager.GANManager):
       segs = self._segments()
       opt = self._optimizer_stream(dev)
       main = torch.cuda.current_stream(dev)
-      ev = d_done
-      if ev is None:
-        ev = torch.cuda.Event()
-        ev.record()
+      ev = torch.cuda.Event()
+      ev.record()
       with torch.cuda.stream(opt):   # discriminator: its gradients are final behind pass 1
         opt.wait_event(ev)
         self._update_all(self.d_optimizer, False, None, 0.0)
@@ -381,11 +333,8 @@ class GAN(gan_manager.GANManager):
         t0, t1, e0, e1 = segs[name]
         done = torch.cuda.Event()
         done.record()   # on the stream that ran the module's backward (main or a decoder branch)
-        wdone = ctx_g.wgrad_event()   # ... and behind its weight gradients
         with torch.cuda.stream(opt):
           opt.wait_event(done)
-          if wdone is not None:
-            opt.wait_event(wdone)
           nn.flush_wgrad_reduces(ctx_g)   # (the module's deferred split reductions, one launch)
           G.spectral.backward_fixup(prefix=G.SEGMENTS[name], dots_only=FUSED_SN_CLIP)
           if not (FUSED_CLIP_ADAM and self.g_optimizer.clip_apply(
@@ -396,7 +345,7 @@ class GAN(gan_manager.GANManager):
           # over, nothing reads the old copies any more): 315 launches leave the critical path
           self._operand_group(G, name, ctx_g.dtype).prep(G.store.version + 1)
       ctx_g.on_segment = segment_done
-      if DEFER_WGRAD_REDUCE and ctx_g.wgrad_stream is None:
+      if DEFER_WGRAD_REDUCE:
         ctx_g.wgrad_defer = []
       ctx_g.backward()
       ctx_g.on_segment = None
@@ -412,7 +361,7 @@ class GAN(gan_manager.GANManager):
       # reductions of ALL weight gradients go out as one table-driven launch behind the backward
       # pass, the operand copies of a model as one launch behind its update (round 5: 295 + 290
       # launches per step less on this path too)
-      if DEFER_WGRAD_REDUCE and ctx_g.wgrad_stream is None:
+      if DEFER_WGRAD_REDUCE:
         ctx_g.wgrad_defer = []
       ctx_g.backward()
       ctx_g.wgrad_defer = None
@@ -447,7 +396,6 @@ class GAN(gan_manager.GANManager):
           sync.reduce_range(G.store.grad, e0, e1)   # (its `ready` event lands on this stream)
       ctx_g.on_segment = segment_done
       ctx_g.after_collective = sync.pump
-      assert ctx_g.wgrad_stream is None   # (see above: one replica only)
       if DEFER_WGRAD_REDUCE:
         ctx_g.wgrad_defer = []
       ctx_g.backward()

@@ -40,13 +40,9 @@ OWNERS = {
     'SE3DS_CHECK_PROMISE': ('tests/test_warp_gpu.py', '_CHECK_PROMISE_SYNC'),
     # the step's schedule (models/image_models.py, trainers/)
     'SE3DS_DUAL_STREAM': ('tools/step_compare.py', 'SE3DS_DUAL_STREAM'),
-    'SE3DS_DUAL_PHASES': ('tools/step_compare.py', 'SE3DS_DUAL_PHASES'),
     'SE3DS_SEGMENT_OPTIMIZER': ('tools/step_compare.py', 'SE3DS_SEGMENT_OPTIMIZER'),
     'SE3DS_FUSED_CLIP_ADAM': ('tools/step_compare.py', 'SE3DS_FUSED_CLIP_ADAM'),
     'SE3DS_DEFER_WGRAD_REDUCE': ('tools/step_compare.py', 'SE3DS_DEFER_WGRAD_REDUCE'),
-    'SE3DS_WGRAD_STREAM': ('tools/step_compare.py', 'SE3DS_WGRAD_STREAM'),
-    'SE3DS_D_OVERLAP': ('tools/step_compare.py', 'SE3DS_D_OVERLAP'),
-    'SE3DS_CU_MASK': ('tools/probes/cu_mask_ab.sh', 'SE3DS_CU_MASK'),
     'SE3DS_UNFUSED_EMA': ('tests/test_nets_gpu.py', 'SE3DS_UNFUSED_EMA'),
     # several replicas
     'SE3DS_DUAL_STREAM_DP': ('tests/test_dist_gpu.py', 'SE3DS_DUAL_STREAM_DP'),
