@@ -371,6 +371,17 @@ int se3ds_wgrad_reduce_tile(void);
 /* n / d as the convolution kernels compute it for tile row -> (image, row, column): the host-made
  * multiplier and shifts, evaluated on the host (test hook: no device work).  d >= 1. */
 uint32_t se3ds_fastdiv_host(uint32_t n, uint32_t d);
+/* Which kernel the convolution dispatchers chose (test hooks: host only, no device work, per host
+ * thread).  Every launch of the family -- forward / data gradient / weight gradient and its split
+ * reduction, the swapped weight gradient and its helpers, weight prep -- records one small integer
+ * that names the template instantiation (tile shape, MFMA shape, dtype, mode, fused-BN flag).
+ * _last_conv_route: the calling thread's most recent launch, -1 before the first.
+ * _conv_route_history(back): the launch `back` launches earlier (0 = the last; the ring keeps 8).
+ * _conv_route_name(route): its name, or NULL for route < 0 or past the last route -- iterate from 0
+ * to enumerate all routes (tests/test_conv_lattice_gpu.py keeps one bit-exact case per name). */
+int se3ds_debug_last_conv_route(void);
+int se3ds_debug_conv_route_history(int back);
+const char* se3ds_debug_conv_route_name(int route);
 
 /* Weight gradient of a THIN-Cout (cout <= 16), stride-1, same-size conv (the generator's
  * 128->3 / 128->1 output convs, image_models.py:93-104) computed with the operand roles

@@ -4164,6 +4164,12 @@ weight_prep_vec_kernel(const float* __restrict__ w, int64_t K, int Cout, uint16_
   }
 }
 
+// se3ds_debug_last_conv_route / se3ds_debug_conv_route_history: the calling host thread's last
+// kRouteRing launches of this family, newest at t_route_ring[(t_route_n - 1) % kRouteRing]
+constexpr int kRouteRing = 8;
+static thread_local int t_route_ring[kRouteRing];
+static thread_local unsigned t_route_n = 0;
+
 // se3ds_conv2d_wgrad_partial: the calling host thread's next split reduction is not launched but
 // described in this row [slabs, splits, n / 4, destination, 1] (when the 16-byte kernel applies)
 static thread_local int64_t* t_defer_row = nullptr;
@@ -4181,11 +4187,11 @@ static void launch_wgrad_reduce(const float* part, int splits, int64_t n, int ac
     return;
   }
   if ((n % 4) == 0 && (((uintptr_t)part | (uintptr_t)out) & 15) == 0)
-    hipLaunchKernelGGL(wgrad_reduce_vec_kernel, dim3(grid_for(n / 4, 256)), dim3(256), 0, s, part,
-                       splits, n / 4, accumulate, out_scale, out);
+    SE3DS_LAUNCH(wgrad_reduce_vec, wgrad_reduce_vec_kernel, dim3(grid_for(n / 4, 256)), dim3(256),
+                 0, s, part, splits, n / 4, accumulate, out_scale, out);
   else
-    hipLaunchKernelGGL(wgrad_reduce_scalar_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, part,
-                       splits, n, accumulate, out_scale, out);
+    SE3DS_LAUNCH(wgrad_reduce_scalar, wgrad_reduce_scalar_kernel, dim3(grid_for(n, 256)), dim3(256),
+                 0, s, part, splits, n, accumulate, out_scale, out);
 }
 
 int fill_classes(IgemmParams& p, int mode, int bm = BM) {
@@ -4220,6 +4226,9 @@ int fill_classes(IgemmParams& p, int mode, int bm = BM) {
 }
 
 }  // namespace
+
+void note_conv_route(int route) { t_route_ring[t_route_n++ % kRouteRing] = route; }
+
 }  // namespace se3ds
 
 using namespace se3ds;
@@ -4372,7 +4381,7 @@ static int conv_common(int mode, const void* src, const void* w, void* out, int 
       thin_on()) {
     int64_t blocks = (int64_t)p.N * ceil_div(p.oH, kThinSRows) * ceil_div(p.oW, kThinSCols);
     if (blocks > 2 * 256) blocks = 2 * 256;   // persistent, two workgroups per CU
-    hipLaunchKernelGGL(thin_s2_dgrad_kernel, dim3((unsigned)blocks), dim3(256), 0, s, p);
+    SE3DS_LAUNCH(thin_s2_dgrad, thin_s2_dgrad_kernel, dim3((unsigned)blocks), dim3(256), 0, s, p);
     return check_launch("conv2d_dgrad(thin s2)");
   }
   if (mode == MODE_FWD && dtype == SE3DS_BF16 && cin <= kThinCinMax && (cout % 128) == 0 &&
@@ -4389,8 +4398,8 @@ static int conv_common(int mode, const void* src, const void* w, void* out, int 
     int64_t blocks = (int64_t)p.N * ceil_div(p.oH, kThinFRows) * ceil_div(p.oW, kThinCols);
     const int64_t resident = 256;   // persistent: one 8-wave workgroup per CU (register bound)
     if (blocks > resident) blocks = resident;
-    hipLaunchKernelGGL(thin_cin_fwd_kernel, dim3((unsigned)blocks), dim3(kThinFThreads), L.bytes, s,
-                       p);
+    SE3DS_LAUNCH(thin_cin_fwd, thin_cin_fwd_kernel, dim3((unsigned)blocks), dim3(kThinFThreads),
+                 L.bytes, s, p);
     return check_launch("conv2d_fwd(thin cin)");
   }
   if (mode == MODE_DGRAD && dtype == SE3DS_BF16 && kh == 3 && kw == 3 && stride == 1 && cout <= 4 &&
@@ -4400,7 +4409,7 @@ static int conv_common(int mode, const void* src, const void* w, void* out, int 
     // persistent: two workgroups per CU (236 registers per lane: the third does not fit, and a grid
     // of three per CU ran its last third at half occupancy)
     if (blocks > 2 * 256) blocks = 2 * 256;
-    hipLaunchKernelGGL(thin_cout_dgrad_kernel, dim3((unsigned)blocks), dim3(256), 0, s, p);
+    SE3DS_LAUNCH(thin_cout_dgrad, thin_cout_dgrad_kernel, dim3((unsigned)blocks), dim3(256), 0, s, p);
     return check_launch("conv2d_dgrad(thin)");
   }
   if (mode == MODE_FWD && dtype == SE3DS_BF16 && kh == 3 && kw == 3 && stride == 1 && cout <= 4 &&
@@ -4416,7 +4425,7 @@ static int conv_common(int mode, const void* src, const void* w, void* out, int 
     }
     int64_t blocks = (int64_t)p.N * ceil_div(p.oH, kThinRows) * ceil_div(p.oW, kThinCols);
     if (blocks > 2 * 256) blocks = 2 * 256;   // persistent: two workgroups per CU
-    hipLaunchKernelGGL(thin_cout_fwd_kernel, dim3((unsigned)blocks), dim3(256), lds, s, p);
+    SE3DS_LAUNCH(thin_cout_fwd, thin_cout_fwd_kernel, dim3((unsigned)blocks), dim3(256), lds, s, p);
     return check_launch("conv2d_fwd(thin)");
   }
   if (glds && dtype == SE3DS_BF16 && stride == 1 && kh == 3 && kw == 3) {
@@ -4427,21 +4436,21 @@ static int conv_common(int mode, const void* src, const void* w, void* out, int 
       const int64_t items = (int64_t)p.N * p.halo_ty * p.halo_tx * (p.oC / co);
       dim3 grid((unsigned)(items < 256 ? items : 256));   // persistent: one workgroup per CU
       if (co == 256 && halo_m16()) {
-        if (mode == MODE_FWD) hipLaunchKernelGGL((igemm_halo_kernel<MODE_FWD, 256, 2, false, true>), grid, dim3(512), 0, s, p);
-        else if (p.bn_x) hipLaunchKernelGGL((igemm_halo_kernel<MODE_DGRAD, 256, 2, true, true>), grid, dim3(512), 0, s, p);
-        else hipLaunchKernelGGL((igemm_halo_kernel<MODE_DGRAD, 256, 2, false, true>), grid, dim3(512), 0, s, p);
+        if (mode == MODE_FWD) SE3DS_LAUNCH(halo256_fwd_m16, (igemm_halo_kernel<MODE_FWD, 256, 2, false, true>), grid, dim3(512), 0, s, p);
+        else if (p.bn_x) SE3DS_LAUNCH(halo256_dgrad_bn_m16, (igemm_halo_kernel<MODE_DGRAD, 256, 2, true, true>), grid, dim3(512), 0, s, p);
+        else SE3DS_LAUNCH(halo256_dgrad_m16, (igemm_halo_kernel<MODE_DGRAD, 256, 2, false, true>), grid, dim3(512), 0, s, p);
       } else if (co == 256) {
-        if (mode == MODE_FWD) hipLaunchKernelGGL((igemm_halo_kernel<MODE_FWD, 256, 2>), grid, dim3(512), 0, s, p);
-        else if (p.bn_x) hipLaunchKernelGGL((igemm_halo_kernel<MODE_DGRAD, 256, 2, true>), grid, dim3(512), 0, s, p);
-        else hipLaunchKernelGGL((igemm_halo_kernel<MODE_DGRAD, 256, 2>), grid, dim3(512), 0, s, p);
+        if (mode == MODE_FWD) SE3DS_LAUNCH(halo256_fwd_m32, (igemm_halo_kernel<MODE_FWD, 256, 2>), grid, dim3(512), 0, s, p);
+        else if (p.bn_x) SE3DS_LAUNCH(halo256_dgrad_bn_m32, (igemm_halo_kernel<MODE_DGRAD, 256, 2, true>), grid, dim3(512), 0, s, p);
+        else SE3DS_LAUNCH(halo256_dgrad_m32, (igemm_halo_kernel<MODE_DGRAD, 256, 2>), grid, dim3(512), 0, s, p);
       } else {
         if (halo_m16()) {
-          if (mode == MODE_FWD) hipLaunchKernelGGL((igemm_halo_kernel<MODE_FWD, 128, 3, false, true>), grid, dim3(512), 0, s, p);
-          else if (p.bn_x) hipLaunchKernelGGL((igemm_halo_kernel<MODE_DGRAD, 128, 3, true, true>), grid, dim3(512), 0, s, p);
-          else hipLaunchKernelGGL((igemm_halo_kernel<MODE_DGRAD, 128, 3, false, true>), grid, dim3(512), 0, s, p);
-        } else if (mode == MODE_FWD) hipLaunchKernelGGL((igemm_halo_kernel<MODE_FWD, 128, 3>), grid, dim3(512), 0, s, p);
-        else if (p.bn_x) hipLaunchKernelGGL((igemm_halo_kernel<MODE_DGRAD, 128, 3, true>), grid, dim3(512), 0, s, p);
-        else hipLaunchKernelGGL((igemm_halo_kernel<MODE_DGRAD, 128, 3>), grid, dim3(512), 0, s, p);
+          if (mode == MODE_FWD) SE3DS_LAUNCH(halo128_fwd_m16, (igemm_halo_kernel<MODE_FWD, 128, 3, false, true>), grid, dim3(512), 0, s, p);
+          else if (p.bn_x) SE3DS_LAUNCH(halo128_dgrad_bn_m16, (igemm_halo_kernel<MODE_DGRAD, 128, 3, true, true>), grid, dim3(512), 0, s, p);
+          else SE3DS_LAUNCH(halo128_dgrad_m16, (igemm_halo_kernel<MODE_DGRAD, 128, 3, false, true>), grid, dim3(512), 0, s, p);
+        } else if (mode == MODE_FWD) SE3DS_LAUNCH(halo128_fwd_m32, (igemm_halo_kernel<MODE_FWD, 128, 3>), grid, dim3(512), 0, s, p);
+        else if (p.bn_x) SE3DS_LAUNCH(halo128_dgrad_bn_m32, (igemm_halo_kernel<MODE_DGRAD, 128, 3, true>), grid, dim3(512), 0, s, p);
+        else SE3DS_LAUNCH(halo128_dgrad_m32, (igemm_halo_kernel<MODE_DGRAD, 128, 3>), grid, dim3(512), 0, s, p);
       }
       return check_launch(mode == MODE_FWD ? "conv2d_fwd(halo)" : "conv2d_dgrad(halo)");
     }
@@ -4453,21 +4462,21 @@ static int conv_common(int mode, const void* src, const void* w, void* out, int 
       if (tiles <= 0) return SE3DS_OK;
       dim3 grid((unsigned)tiles, (unsigned)(p.oC / co));
       if (co == 256 && halo_m16()) {
-        if (mode == MODE_FWD) hipLaunchKernelGGL((igemm_big_kernel<MODE_FWD, 256, false, true>), grid, dim3(512), 0, s, p);
-        else if (p.bn_x) hipLaunchKernelGGL((igemm_big_kernel<MODE_DGRAD, 256, true, true>), grid, dim3(512), 0, s, p);
-        else hipLaunchKernelGGL((igemm_big_kernel<MODE_DGRAD, 256, false, true>), grid, dim3(512), 0, s, p);
+        if (mode == MODE_FWD) SE3DS_LAUNCH(big256_fwd_m16, (igemm_big_kernel<MODE_FWD, 256, false, true>), grid, dim3(512), 0, s, p);
+        else if (p.bn_x) SE3DS_LAUNCH(big256_dgrad_bn_m16, (igemm_big_kernel<MODE_DGRAD, 256, true, true>), grid, dim3(512), 0, s, p);
+        else SE3DS_LAUNCH(big256_dgrad_m16, (igemm_big_kernel<MODE_DGRAD, 256, false, true>), grid, dim3(512), 0, s, p);
       } else if (co == 256) {
-        if (mode == MODE_FWD) hipLaunchKernelGGL((igemm_big_kernel<MODE_FWD, 256>), grid, dim3(512), 0, s, p);
-        else if (p.bn_x) hipLaunchKernelGGL((igemm_big_kernel<MODE_DGRAD, 256, true>), grid, dim3(512), 0, s, p);
-        else hipLaunchKernelGGL((igemm_big_kernel<MODE_DGRAD, 256>), grid, dim3(512), 0, s, p);
+        if (mode == MODE_FWD) SE3DS_LAUNCH(big256_fwd_m32, (igemm_big_kernel<MODE_FWD, 256>), grid, dim3(512), 0, s, p);
+        else if (p.bn_x) SE3DS_LAUNCH(big256_dgrad_bn_m32, (igemm_big_kernel<MODE_DGRAD, 256, true>), grid, dim3(512), 0, s, p);
+        else SE3DS_LAUNCH(big256_dgrad_m32, (igemm_big_kernel<MODE_DGRAD, 256>), grid, dim3(512), 0, s, p);
       } else if (halo_m16()) {
-        if (mode == MODE_FWD) hipLaunchKernelGGL((igemm_big_kernel<MODE_FWD, 128, false, true>), grid, dim3(512), 0, s, p);
-        else if (p.bn_x) hipLaunchKernelGGL((igemm_big_kernel<MODE_DGRAD, 128, true, true>), grid, dim3(512), 0, s, p);
-        else hipLaunchKernelGGL((igemm_big_kernel<MODE_DGRAD, 128, false, true>), grid, dim3(512), 0, s, p);
+        if (mode == MODE_FWD) SE3DS_LAUNCH(big128_fwd_m16, (igemm_big_kernel<MODE_FWD, 128, false, true>), grid, dim3(512), 0, s, p);
+        else if (p.bn_x) SE3DS_LAUNCH(big128_dgrad_bn_m16, (igemm_big_kernel<MODE_DGRAD, 128, true, true>), grid, dim3(512), 0, s, p);
+        else SE3DS_LAUNCH(big128_dgrad_m16, (igemm_big_kernel<MODE_DGRAD, 128, false, true>), grid, dim3(512), 0, s, p);
       } else {
-        if (mode == MODE_FWD) hipLaunchKernelGGL((igemm_big_kernel<MODE_FWD, 128>), grid, dim3(512), 0, s, p);
-        else if (p.bn_x) hipLaunchKernelGGL((igemm_big_kernel<MODE_DGRAD, 128, true>), grid, dim3(512), 0, s, p);
-        else hipLaunchKernelGGL((igemm_big_kernel<MODE_DGRAD, 128>), grid, dim3(512), 0, s, p);
+        if (mode == MODE_FWD) SE3DS_LAUNCH(big128_fwd_m32, (igemm_big_kernel<MODE_FWD, 128>), grid, dim3(512), 0, s, p);
+        else if (p.bn_x) SE3DS_LAUNCH(big128_dgrad_bn_m32, (igemm_big_kernel<MODE_DGRAD, 128, true>), grid, dim3(512), 0, s, p);
+        else SE3DS_LAUNCH(big128_dgrad_m32, (igemm_big_kernel<MODE_DGRAD, 128>), grid, dim3(512), 0, s, p);
       }
       return check_launch(mode == MODE_FWD ? "conv2d_fwd(big)" : "conv2d_dgrad(big)");
     }
@@ -4477,26 +4486,26 @@ static int conv_common(int mode, const void* src, const void* w, void* out, int 
   dim3 grid((unsigned)tiles, (unsigned)ceil_div(p.oC, BN));
   if (glds) {
     if (dtype == SE3DS_F32) {
-      if (mode == MODE_FWD) hipLaunchKernelGGL((igemm_glds_kernel<float, MODE_FWD>), grid, dim3(kThreads), 0, s, p);
-      else hipLaunchKernelGGL((igemm_glds_kernel<float, MODE_DGRAD>), grid, dim3(kThreads), 0, s, p);
+      if (mode == MODE_FWD) SE3DS_LAUNCH(glds_f32_fwd, (igemm_glds_kernel<float, MODE_FWD>), grid, dim3(kThreads), 0, s, p);
+      else SE3DS_LAUNCH(glds_f32_dgrad, (igemm_glds_kernel<float, MODE_DGRAD>), grid, dim3(kThreads), 0, s, p);
     } else {
       // (the 16x16x32 epilogue has no ragged channel tiles)
       if ((p.oC % BN) == 0 && halo_m16()) {
-        if (mode == MODE_FWD) hipLaunchKernelGGL((igemm_glds_kernel<uint16_t, MODE_FWD, false, true>), grid, dim3(kThreads), 0, s, p);
-        else if (p.bn_x) hipLaunchKernelGGL((igemm_glds_kernel<uint16_t, MODE_DGRAD, true, true>), grid, dim3(kThreads), 0, s, p);
-        else hipLaunchKernelGGL((igemm_glds_kernel<uint16_t, MODE_DGRAD, false, true>), grid, dim3(kThreads), 0, s, p);
-      } else if (mode == MODE_FWD) hipLaunchKernelGGL((igemm_glds_kernel<uint16_t, MODE_FWD>), grid, dim3(kThreads), 0, s, p);
-      else if (p.bn_x) hipLaunchKernelGGL((igemm_glds_kernel<uint16_t, MODE_DGRAD, true>), grid, dim3(kThreads), 0, s, p);
-      else hipLaunchKernelGGL((igemm_glds_kernel<uint16_t, MODE_DGRAD>), grid, dim3(kThreads), 0, s, p);
+        if (mode == MODE_FWD) SE3DS_LAUNCH(glds_bf16_fwd_m16, (igemm_glds_kernel<uint16_t, MODE_FWD, false, true>), grid, dim3(kThreads), 0, s, p);
+        else if (p.bn_x) SE3DS_LAUNCH(glds_bf16_dgrad_bn_m16, (igemm_glds_kernel<uint16_t, MODE_DGRAD, true, true>), grid, dim3(kThreads), 0, s, p);
+        else SE3DS_LAUNCH(glds_bf16_dgrad_m16, (igemm_glds_kernel<uint16_t, MODE_DGRAD, false, true>), grid, dim3(kThreads), 0, s, p);
+      } else if (mode == MODE_FWD) SE3DS_LAUNCH(glds_bf16_fwd_m32, (igemm_glds_kernel<uint16_t, MODE_FWD>), grid, dim3(kThreads), 0, s, p);
+      else if (p.bn_x) SE3DS_LAUNCH(glds_bf16_dgrad_bn_m32, (igemm_glds_kernel<uint16_t, MODE_DGRAD, true>), grid, dim3(kThreads), 0, s, p);
+      else SE3DS_LAUNCH(glds_bf16_dgrad_m32, (igemm_glds_kernel<uint16_t, MODE_DGRAD>), grid, dim3(kThreads), 0, s, p);
     }
     return check_launch(mode == MODE_FWD ? "conv2d_fwd(glds)" : "conv2d_dgrad(glds)");
   }
   if (dtype == SE3DS_F32) {
-    if (mode == MODE_FWD) hipLaunchKernelGGL((igemm_kernel<float, MODE_FWD>), grid, dim3(kThreads), 0, s, p);
-    else hipLaunchKernelGGL((igemm_kernel<float, MODE_DGRAD>), grid, dim3(kThreads), 0, s, p);
+    if (mode == MODE_FWD) SE3DS_LAUNCH(igemm_f32_fwd, (igemm_kernel<float, MODE_FWD>), grid, dim3(kThreads), 0, s, p);
+    else SE3DS_LAUNCH(igemm_f32_dgrad, (igemm_kernel<float, MODE_DGRAD>), grid, dim3(kThreads), 0, s, p);
   } else {
-    if (mode == MODE_FWD) hipLaunchKernelGGL((igemm_kernel<uint16_t, MODE_FWD>), grid, dim3(kThreads), 0, s, p);
-    else hipLaunchKernelGGL((igemm_kernel<uint16_t, MODE_DGRAD>), grid, dim3(kThreads), 0, s, p);
+    if (mode == MODE_FWD) SE3DS_LAUNCH(igemm_bf16_fwd, (igemm_kernel<uint16_t, MODE_FWD>), grid, dim3(kThreads), 0, s, p);
+    else SE3DS_LAUNCH(igemm_bf16_dgrad, (igemm_kernel<uint16_t, MODE_DGRAD>), grid, dim3(kThreads), 0, s, p);
   }
   return check_launch(mode == MODE_FWD ? "conv2d_fwd" : "conv2d_dgrad");
 }
@@ -4703,10 +4712,10 @@ int se3ds_conv2d_wgrad(const void* x, const void* dy, float* dw, int dtype, int 
       q.dy_cstride = cout; q.co_valid = cout;
       dim3 tgrid((unsigned)(cin / 64), (unsigned)(cout / 128), (unsigned)tsplits);
       if (!wrap_w)
-        if (halo_m16()) hipLaunchKernelGGL(wgrad_taps3_kernel<true>, tgrid, dim3(512), 0, s, q);
-        else hipLaunchKernelGGL(wgrad_taps3_kernel<false>, tgrid, dim3(512), 0, s, q);
+        if (halo_m16()) SE3DS_LAUNCH(wgrad_taps3_m16, wgrad_taps3_kernel<true>, tgrid, dim3(512), 0, s, q);
+        else SE3DS_LAUNCH(wgrad_taps3_m32, wgrad_taps3_kernel<false>, tgrid, dim3(512), 0, s, q);
       else
-        hipLaunchKernelGGL(wgrad_taps_kernel, tgrid, dim3(512), 0, s, q);
+        SE3DS_LAUNCH(wgrad_taps_wrap, wgrad_taps_kernel, tgrid, dim3(512), 0, s, q);
       const int64_t tnel = (int64_t)9 * cin * cout;
       launch_wgrad_reduce((const float*)workspace, tsplits, tnel, accumulate, out_scale, dw, s);
       return check_launch("conv2d_wgrad(taps)");
@@ -4728,7 +4737,7 @@ int se3ds_conv2d_wgrad(const void* x, const void* dy, float* dw, int dtype, int 
     }
     int64_t blocks = (int64_t)n * ceil_div(ho, kThinWRows) * ceil_div(wo, kThinCols);
     if (blocks > 256) blocks = 256;
-    hipLaunchKernelGGL(thin_cin_wgrad_kernel, dim3((unsigned)blocks), dim3(kThinWThreads), lds, s, q);
+    SE3DS_LAUNCH(thin_cin_wgrad, thin_cin_wgrad_kernel, dim3((unsigned)blocks), dim3(kThinWThreads), lds, s, q);
     const int64_t tnel = (int64_t)kh * kw * cin * cout;
     launch_wgrad_reduce((const float*)workspace, (int)blocks, tnel, accumulate, out_scale, dw, s);
     return check_launch("conv2d_wgrad(thin cin)");
@@ -4753,12 +4762,12 @@ int se3ds_conv2d_wgrad(const void* x, const void* dy, float* dw, int dtype, int 
                     (cin % epc) == 0 && (cout % epc) == 0;
   if (glds) {
     p.l_per_split = ceil_div(ceil_div(L, p.splits), 64) * 64;
-    if (dtype == SE3DS_F32) hipLaunchKernelGGL(wgrad_glds_kernel<float>, grid, dim3(kThreads), 0, s, p);
-    else hipLaunchKernelGGL(wgrad_glds_kernel<uint16_t>, grid, dim3(kThreads), 0, s, p);
+    if (dtype == SE3DS_F32) SE3DS_LAUNCH(wgrad_glds_f32, wgrad_glds_kernel<float>, grid, dim3(kThreads), 0, s, p);
+    else SE3DS_LAUNCH(wgrad_glds_bf16, wgrad_glds_kernel<uint16_t>, grid, dim3(kThreads), 0, s, p);
   } else if (dtype == SE3DS_F32) {
-    hipLaunchKernelGGL(wgrad_kernel<float>, grid, dim3(kThreads), 0, s, p);
+    SE3DS_LAUNCH(wgrad_f32, wgrad_kernel<float>, grid, dim3(kThreads), 0, s, p);
   } else {
-    hipLaunchKernelGGL(wgrad_kernel<uint16_t>, grid, dim3(kThreads), 0, s, p);
+    SE3DS_LAUNCH(wgrad_bf16, wgrad_kernel<uint16_t>, grid, dim3(kThreads), 0, s, p);
   }
   const int64_t nel = (int64_t)kh * kw * cin * cout;
   launch_wgrad_reduce((const float*)workspace, p.splits, nel, accumulate, out_scale, dw, s);
@@ -4783,8 +4792,8 @@ int se3ds_conv2d_wgrad_partial(const void* x, const void* dy, float* dw, int dty
 int se3ds_wgrad_reduce_multi(const int64_t* table, int rows, int64_t workgroups, void* stream) {
   if (rows <= 0 || workgroups <= 0) return SE3DS_OK;
   if (workgroups >= ((int64_t)1 << 31)) return SE3DS_E_BADSHAPE;
-  hipLaunchKernelGGL(wgrad_reduce_multi_kernel, dim3((unsigned)workgroups), dim3(256), 0,
-                     as_stream(stream), table, rows);
+  SE3DS_LAUNCH(wgrad_reduce_multi, wgrad_reduce_multi_kernel, dim3((unsigned)workgroups), dim3(256),
+               0, as_stream(stream), table, rows);
   return check_launch("wgrad_reduce_multi");
 }
 
@@ -4851,8 +4860,8 @@ int se3ds_conv2d_wgrad_swapped(const void* x, const void* dy, float* dw, int dty
         return SE3DS_E_LAUNCH;                                                                    \
       lds_set = lds;                                                                              \
     }                                                                                             \
-    hipLaunchKernelGGL(thin_cout_wgrad_kernel<M>, dim3((unsigned)blocks), dim3(kThinWThreads), lds, \
-                       s, q);                                                                     \
+    SE3DS_LAUNCH(thin_cout_wgrad_t##M, thin_cout_wgrad_kernel<M>, dim3((unsigned)blocks),         \
+                 dim3(kThinWThreads), lds, s, q);                                                 \
   } while (0)
     switch (tiles_per_wave) {
       case 2: SE3DS_THIN_CW(2); break;
@@ -4873,8 +4882,8 @@ int se3ds_conv2d_wgrad_swapped(const void* x, const void* dy, float* dw, int dty
       const int64_t px = (int64_t)n * h * w;
       uint16_t* dyp = (uint16_t*)workspace;
       float* part = (float*)((char*)workspace + ((size_t)px * 16 + 255) / 256 * 256);
-      hipLaunchKernelGGL(pad_channels8_kernel, dim3(grid_for(px, 256)), dim3(256), 0, s,
-                         (const uint16_t*)dy, cout, px, dyp);
+      SE3DS_LAUNCH(pad_channels8, pad_channels8_kernel, dim3(grid_for(px, 256)), dim3(256), 0, s,
+                   (const uint16_t*)dy, cout, px, dyp);
       WgradTapsParams q;
       q.x = (const uint16_t*)x; q.H = h; q.W = w; q.Cin = cin;
       q.dy = dyp; q.Ho = h; q.Wo = w; q.Cout = cout;
@@ -4885,7 +4894,7 @@ int se3ds_conv2d_wgrad_swapped(const void* x, const void* dy, float* dw, int dty
       q.steps_per_split = ceil_div(tsteps, tsplits);
       q.dy_cstride = 8; q.co_valid = cout;
       dim3 tgrid((unsigned)(cin / 64), 1, (unsigned)tsplits);
-      hipLaunchKernelGGL(wgrad_taps_kernel, tgrid, dim3(512), 0, s, q);
+      SE3DS_LAUNCH(wgrad_taps_thin, wgrad_taps_kernel, tgrid, dim3(512), 0, s, q);
       const int64_t tnel = (int64_t)9 * cin * cout;
       launch_wgrad_reduce((const float*)part, tsplits, tnel, accumulate, nullptr, dw, s);
       return check_launch("conv2d_wgrad(taps, thin)");
@@ -4898,9 +4907,28 @@ int se3ds_conv2d_wgrad_swapped(const void* x, const void* dy, float* dw, int dty
                               k - 1 - pad, 0, nullptr, 0, nullptr, nullptr, 0,
                               (char*)workspace + tmp_bytes, workspace_bytes - tmp_bytes, stream);
   if (rc != SE3DS_OK) return rc;
-  hipLaunchKernelGGL(wgrad_swap_fixup_kernel, dim3(grid_for((int64_t)k * k * cin * cout, 256)),
-                     dim3(256), 0, as_stream(stream), tmp, k, cin, cout, accumulate, dw);
+  SE3DS_LAUNCH(wgrad_swap_fixup, wgrad_swap_fixup_kernel,
+               dim3(grid_for((int64_t)k * k * cin * cout, 256)), dim3(256), 0, as_stream(stream),
+               tmp, k, cin, cout, accumulate, dw);
   return check_launch("conv2d_wgrad_swapped");
+}
+
+// Test hooks, host only: which kernel instantiation the calling thread's dispatchers launched last
+// (back = 0) or `back` launches before that (an entry point may launch several: the weight gradient
+// its split reduction, the 2x2 transposed conv one pass per row parity); -1 = no such launch (none
+// yet, or further back than the ring of 8 remembers).  Names: NULL past the last route.
+int se3ds_debug_conv_route_history(int back) {
+  if (back < 0 || back >= kRouteRing || (unsigned)back >= t_route_n) return -1;
+  return t_route_ring[(t_route_n - 1 - (unsigned)back) % kRouteRing];
+}
+int se3ds_debug_last_conv_route(void) { return se3ds_debug_conv_route_history(0); }
+const char* se3ds_debug_conv_route_name(int route) {
+  static const char* const kNames[] = {
+#define SE3DS_ROUTE_NAME(name) #name,
+      SE3DS_CONV_ROUTES(SE3DS_ROUTE_NAME)
+#undef SE3DS_ROUTE_NAME
+  };
+  return route >= 0 && route < kConvRouteCount ? kNames[route] : nullptr;
 }
 
 int se3ds_weight_prep(const float* w, int64_t k, int cout, int dtype, void* wt, void* wn,
@@ -4909,15 +4937,16 @@ int se3ds_weight_prep(const float* w, int64_t k, int cout, int dtype, void* wt, 
   dim3 grid((unsigned)ceil_div(k, 32), (unsigned)ceil_div(cout, 32));
   hipStream_t s = as_stream(stream);
   if (dtype == SE3DS_F32)
-    hipLaunchKernelGGL(weight_prep_kernel<float>, grid, dim3(256), 0, s, w, k, cout, (float*)wt,
-                       (float*)wn);
+    SE3DS_LAUNCH(weight_prep_f32, weight_prep_kernel<float>, grid, dim3(256), 0, s, w, k, cout,
+                 (float*)wt, (float*)wn);
   else if (dtype == SE3DS_BF16 && (cout % 4) == 0 && (k % 8) == 0 &&
            (((uintptr_t)w | (uintptr_t)wt) & 15) == 0 && (((uintptr_t)wn) & 7) == 0)
-    hipLaunchKernelGGL(weight_prep_vec_kernel, dim3((unsigned)ceil_div(k, 64), (unsigned)ceil_div(cout, 64)),
-                       dim3(256), 0, s, w, k, cout, (uint16_t*)wt, (uint16_t*)wn);
+    SE3DS_LAUNCH(weight_prep_vec, weight_prep_vec_kernel,
+                 dim3((unsigned)ceil_div(k, 64), (unsigned)ceil_div(cout, 64)), dim3(256), 0, s, w,
+                 k, cout, (uint16_t*)wt, (uint16_t*)wn);
   else if (dtype == SE3DS_BF16)
-    hipLaunchKernelGGL(weight_prep_kernel<uint16_t>, grid, dim3(256), 0, s, w, k, cout,
-                       (uint16_t*)wt, (uint16_t*)wn);
+    SE3DS_LAUNCH(weight_prep_bf16, weight_prep_kernel<uint16_t>, grid, dim3(256), 0, s, w, k, cout,
+                 (uint16_t*)wt, (uint16_t*)wn);
   else
     return SE3DS_E_BADDTYPE;
   return check_launch("weight_prep");

@@ -772,8 +772,8 @@ int se3ds_quantize(const void* in, int in_dtype, int64_t n, int pre_clamp, float
 int se3ds_weight_prep_multi(const int64_t* table, int nlayers, int64_t total_tiles, void* stream) {
   if (nlayers <= 0 || total_tiles <= 0) return SE3DS_OK;
   if (total_tiles >= ((int64_t)1 << 31)) return SE3DS_E_BADSHAPE;
-  hipLaunchKernelGGL(weight_prep_multi_kernel, dim3((unsigned)total_tiles), dim3(256), 0,
-                     as_stream(stream), table, nlayers);
+  SE3DS_LAUNCH(weight_prep_multi, weight_prep_multi_kernel, dim3((unsigned)total_tiles), dim3(256), 0,
+               as_stream(stream), table, nlayers);
   return check_launch("weight_prep_multi");
 }
 

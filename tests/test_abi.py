@@ -62,3 +62,28 @@ def test_fastdiv_matches_integer_division():
     for n in ns:
       if 0 <= n < 2 ** 32:
         assert L.se3ds_fastdiv_host(n, d) == n // d, (n, d)
+
+
+def test_conv_route_report_names_are_unique_and_end_with_null():
+  """se3ds_debug_conv_route_name enumerates the convolution family's kernel instantiations (host
+  only); tests/test_conv_lattice_gpu.py keeps one bit-exact case per name.  Before any launch of the
+  calling thread the report is -1, as is a look further back than the ring remembers."""
+  import se3ds_amd.hipops  # noqa: F401
+  L = _lib.lib()
+  names, i = [], 0
+  while L.se3ds_debug_conv_route_name(i) is not None:
+    names.append(L.se3ds_debug_conv_route_name(i).decode())
+    i += 1
+  assert len(names) == len(set(names)) >= 60
+  assert L.se3ds_debug_conv_route_name(-1) is None and L.se3ds_debug_conv_route_name(len(names)) is None
+  for family in ('halo256_fwd_m16', 'big128_dgrad_bn_m32', 'glds_f32_fwd', 'igemm_bf16_dgrad',
+                 'wgrad_taps3_m16', 'wgrad_reduce_multi', 'thin_cout_wgrad_t5', 'weight_prep_multi'):
+    assert family in names
+  assert L.se3ds_debug_conv_route_history(8) == -1 and L.se3ds_debug_conv_route_history(-1) == -1
+  # a fresh process has launched nothing: the report is -1
+  import subprocess
+  import sys
+  code = ('import se3ds_amd.hipops; from se3ds_amd import _lib; L = _lib.lib(); '
+          'print(L.se3ds_debug_last_conv_route(), L.se3ds_debug_conv_route_history(0))')
+  r = subprocess.run([sys.executable, '-c', code], cwd=ROOT, capture_output=True, text=True, check=True)
+  assert r.stdout.split() == ['-1', '-1'], r.stdout
