@@ -663,6 +663,21 @@ int se3ds_input_transform(const uint8_t* image, const uint8_t* proj_image, const
                           float* o_proj_depth, float* o_depth, float* o_blurred, int32_t* o_seg,
                           void* stream);
 
+/* datasets/indoor_datasets.py:734-792 (R2RVideoDataset._transform_fn) over the N*T frames of a
+ * batch resident in HBM, one gather: image fp32 (N,T,H0,W0,3) -> o_original fp32 (N,T,h,w,3) by
+ * tf.image.resize bilinear (half-pixel centres, no antialias, NO clip; identity size copies);
+ * o_image = o_original * band mask on the OUTPUT grid (:753-765), hmode [N] = 0 none / 1
+ * start < x < end / 2 x > start or x < end, hband [N][2] = start, end, one row per example shared
+ * by its T frames; o_image NULL: no masked copy is written (hmode / hband may then be NULL).
+ * segmentation / pd_segmentation uint8 (N,T,H0,W0) and depth / pd_depth fp32 (N,T,H0,W0) ->
+ * (N,T,h,w,1) by nearest.  pd_segmentation with o_pd_seg, and pd_depth with o_pd_depth, may be
+ * NULL together.  se3ds_resize's arithmetic: bit-identical to that chain run op by op. */
+int se3ds_video_transform(const float* image, const uint8_t* segmentation,
+                          const uint8_t* pd_segmentation, const float* depth, const float* pd_depth,
+                          const int32_t* hmode, const float* hband, int n, int t, int h0, int w0,
+                          int h, int w, float* o_original, float* o_image, uint8_t* o_seg,
+                          uint8_t* o_pd_seg, float* o_depth, float* o_pd_depth, void* stream);
+
 /* ======================================================================================
  * Inception-v3 evaluator -- utils/inception_utils.py, utils/eval_metric.py EvalMetric
  * (reference utils/inception_utils.py, utils/eval_metric.py:66-343).  csrc/inception.hip.

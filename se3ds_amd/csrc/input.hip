@@ -111,6 +111,106 @@ input_transform_kernel(const InputXf p) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Evaluation input pipeline: R2RVideoDataset._transform_fn (datasets/indoor_datasets.py:734-792)
+// over all N*T frames of a batch -- bilinear resize of the RGB frames (no clip), the optional band
+// mask on the OUTPUT grid (:753-765), nearest resize of the two label and the two depth planes --
+// as one gather, no intermediate tensor.  HBM bound; layout of the work:
+//   * one workgroup per run of kB output pixels of ONE output row, so everything that depends on
+//     the row (frame, example, both source rows, the vertical weight, the band) is wave-uniform and
+//     no thread does a 64-bit division;
+//   * one thread per output pixel: its taps of one source row are the RGB triples x0 and x1, 12 B
+//     each (one dwordx3 load per tap), and neighbouring lanes read neighbouring triples.  At the
+//     exact 2x reduction of the shipped configs x0 = 2x, x1 = 2x + 1: a wave's taps are two runs of
+//     64 x 24 B = 1536 contiguous bytes without holes, every source row is touched by exactly one
+//     output row, so each image byte leaves HBM once (the x0 / x1 loads of a wave share their cache
+//     lines in the vector L1);
+//   * the stores of a wave are contiguous: 768 B of RGB (x1 or x2), 64 B per label plane, 256 B
+//     per depth plane.
+struct VideoXf {
+  const float* image;      // (N,T,H0,W0,3)
+  const uint8_t* seg;      // (N,T,H0,W0)
+  const uint8_t* pd_seg;   // (N,T,H0,W0) or NULL (with o_pd_seg)
+  const float* depth;      // (N,T,H0,W0)
+  const float* pd_depth;   // (N,T,H0,W0) or NULL (with o_pd_depth)
+  const int32_t* hmode;    // [N]: 0 none / 1 start < x < end / 2 x > start or x < end
+  const float* hband;      // [N][2]: start, end (output-grid pixels)
+  int t, h0, w0, h, w;
+  float sy, sx;            // (float)h0 / (float)h, (float)w0 / (float)w: divided once, on the host
+  float* o_original;      // (N,T,h,w,3)
+  float* o_image;          // (N,T,h,w,3) or NULL: no masked copy
+  uint8_t* o_seg;          // (N,T,h,w,1)
+  uint8_t* o_pd_seg;
+  float* o_depth;          // (N,T,h,w,1)
+  float* o_pd_depth;
+};
+
+struct Rgb { float r, g, b; };   // 12 B, 4-byte aligned: one dwordx3 access
+
+__global__ void __launch_bounds__(kB)
+video_transform_kernel(const VideoXf p) {
+  const int bpr = (p.w + kB - 1) / kB;          // workgroups per output row
+  const int row = (int)blockIdx.x / bpr;        // frame * h + y  (< N * T * h by the grid size)
+  const int x = ((int)blockIdx.x - row * bpr) * kB + (int)threadIdx.x;
+  if (x >= p.w) return;
+  const int f = row / p.h, y = row - f * p.h;
+  const float sy = p.sy, sx = p.sx;
+  const int64_t fbase = (int64_t)f * p.h0 * p.w0;   // first pixel of the source frame
+  const int64_t o = (int64_t)row * p.w + x;         // output pixel
+  // ---- nearest planes (tf.image.resize 'nearest', half-pixel centres)
+  int ny = (int)floorf(((float)y + 0.5f) * sy);
+  int nx = (int)floorf(((float)x + 0.5f) * sx);
+  ny = ny < p.h0 - 1 ? ny : p.h0 - 1;
+  nx = nx < p.w0 - 1 ? nx : p.w0 - 1;
+  const int64_t q = fbase + (int64_t)ny * p.w0 + nx;
+  p.o_seg[o] = p.seg[q];
+  p.o_depth[o] = p.depth[q];
+  if (p.pd_seg) p.o_pd_seg[o] = p.pd_seg[q];
+  if (p.pd_depth) p.o_pd_depth[o] = p.pd_depth[q];
+  // ---- bilinear image (tf.image.resize default; the video path does not clip)
+  const float srcy = ((float)y + 0.5f) * sy - 0.5f;
+  const float srcx = ((float)x + 0.5f) * sx - 0.5f;
+  const float fly = floorf(srcy), flx = floorf(srcx);
+  const float wy = srcy - fly, wx = srcx - flx;
+  int y0 = (int)fly, x0 = (int)flx;
+  int y1 = y0 + 1, x1 = x0 + 1;
+  y0 = y0 < 0 ? 0 : (y0 > p.h0 - 1 ? p.h0 - 1 : y0);
+  y1 = y1 < 0 ? 0 : (y1 > p.h0 - 1 ? p.h0 - 1 : y1);
+  x0 = x0 < 0 ? 0 : (x0 > p.w0 - 1 ? p.w0 - 1 : x0);
+  x1 = x1 < 0 ? 0 : (x1 > p.w0 - 1 ? p.w0 - 1 : x1);
+  const Rgb* r0 = reinterpret_cast<const Rgb*>(p.image) + fbase + (int64_t)y0 * p.w0;
+  const Rgb* r1 = reinterpret_cast<const Rgb*>(p.image) + fbase + (int64_t)y1 * p.w0;
+  Rgb v;
+  if (p.h == p.h0 && p.w == p.w0) {
+    v = r0[x0];   // identity size: tf.image.resize returns the input
+  } else {
+    const Rgb tl = r0[x0], tr = r0[x1], bl = r1[x0], br = r1[x1];
+    const float tl_[3] = {tl.r, tl.g, tl.b}, tr_[3] = {tr.r, tr.g, tr.b};
+    const float bl_[3] = {bl.r, bl.g, bl.b}, br_[3] = {br.r, br.g, br.b};
+    float c[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const float top = tl_[k] + (tr_[k] - tl_[k]) * wx;
+      const float bot = bl_[k] + (br_[k] - bl_[k]) * wx;
+      c[k] = top + (bot - top) * wy;
+    }
+    v.r = c[0]; v.g = c[1]; v.b = c[2];
+  }
+  reinterpret_cast<Rgb*>(p.o_original)[o] = v;
+  if (p.o_image) {
+    const int b = f / p.t;
+    const int mode = p.hmode[b];
+    const float start = p.hband[2 * b], end = p.hband[2 * b + 1];
+    const float fx = (float)x;
+    float m = 1.0f;
+    if (mode == 1) m = ((fx > start) && (fx < end)) ? 1.0f : 0.0f;
+    if (mode == 2) m = ((fx > start) || (fx < end)) ? 1.0f : 0.0f;
+    Rgb vm;
+    vm.r = v.r * m; vm.g = v.g * m; vm.b = v.b * m;
+    reinterpret_cast<Rgb*>(p.o_image)[o] = vm;
+  }
+}
+
 }  // namespace
 }  // namespace se3ds
 
@@ -134,4 +234,33 @@ extern "C" int se3ds_input_transform(const uint8_t* image, const uint8_t* proj_i
   hipLaunchKernelGGL(input_transform_kernel, dim3(grid_for((int64_t)n * h * w, kB)), dim3(kB), 0,
                      as_stream(stream), p);
   return check_launch("input_transform");
+}
+
+extern "C" int se3ds_video_transform(const float* image, const uint8_t* segmentation,
+                                     const uint8_t* pd_segmentation, const float* depth,
+                                     const float* pd_depth, const int32_t* hmode,
+                                     const float* hband, int n, int t, int h0, int w0, int h, int w,
+                                     float* o_original, float* o_image, uint8_t* o_seg,
+                                     uint8_t* o_pd_seg, float* o_depth, float* o_pd_depth,
+                                     void* stream) {
+  if (n <= 0 || t <= 0 || h0 <= 0 || w0 <= 0 || h <= 0 || w <= 0) return SE3DS_E_BADSHAPE;
+  // older records lack the pathdreamer planes: input and output come and go together
+  if ((pd_segmentation == nullptr) != (o_pd_seg == nullptr) ||
+      (pd_depth == nullptr) != (o_pd_depth == nullptr))
+    return SE3DS_E_BADSHAPE;
+  if (o_image && (!hmode || !hband)) return SE3DS_E_BADSHAPE;
+  const int64_t rows = (int64_t)n * t * h;
+  const int64_t blocks = rows * ((w + kB - 1) / kB);
+  // rows: int arithmetic in the kernel; blocks * kB: a launch holds fewer than 2^32 threads
+  if (rows > INT32_MAX || blocks * kB > (int64_t)UINT32_MAX) return SE3DS_E_BADSHAPE;
+  VideoXf p;
+  p.image = image; p.seg = segmentation; p.pd_seg = pd_segmentation; p.depth = depth;
+  p.pd_depth = pd_depth; p.hmode = hmode; p.hband = hband;
+  p.t = t; p.h0 = h0; p.w0 = w0; p.h = h; p.w = w;
+  p.sy = (float)h0 / (float)h; p.sx = (float)w0 / (float)w;
+  p.o_original = o_original; p.o_image = o_image; p.o_seg = o_seg; p.o_pd_seg = o_pd_seg;
+  p.o_depth = o_depth; p.o_pd_depth = o_pd_depth;
+  hipLaunchKernelGGL(video_transform_kernel, dim3((unsigned)blocks), dim3(kB), 0, as_stream(stream),
+                     p);
+  return check_launch("video_transform");
 }

@@ -1,12 +1,17 @@
 """GAN training manager -- MI355X implementation of the hot-path half of the reference's
 trainers/gan_manager.py: model / optimizer construction (:169-183), the cluster step
-(:351-385), the EMA hooks (:642-655) and checkpoint save / restore as one .npz.  Dataset
-pipelines, TensorFlow checkpoint bundles, TensorBoard
-logging and the FID evaluation loop of the reference are out of scope;
-`train()` runs the same host loop on a synthetic (or user supplied) batch iterator."""
+(:351-385), the EMA hooks (:642-655) and checkpoint save / restore as one .npz.  TFRecord
+parsing, TensorFlow checkpoint objects and TensorBoard logging are out of scope (SURVEY.md section
+2.1); `train()` runs the same host loop on a synthetic (or user supplied) batch iterator, `test()`
+the reference's evaluation loop (:233-322) over parsed trajectory examples: R2RVideoDataset ->
+EvalMetric -> one scores_<split>.csv row per checkpoint."""
 import abc
+import csv
 import os
 import random
+import re
+import struct
+import zlib
 from typing import Optional
 
 import numpy as np
@@ -203,6 +208,27 @@ class Mean:
     return np.float32(tot / len(self._vals))
 
 
+def _encode_png(pixels: np.ndarray) -> bytes:
+  """8-bit PNG of a uint8 (H,W,1) grey or (H,W,3) RGB array: one IDAT chunk, filter 0 on every
+  row (zlib + struct only; no imaging package is assumed)."""
+  if pixels.dtype != np.uint8 or pixels.ndim != 3 or pixels.shape[2] not in (1, 3):
+    raise ValueError(f'uint8 (H,W,1) or (H,W,3) expected, got {pixels.dtype} {pixels.shape}')
+  h, w, c = pixels.shape
+  rows = np.concatenate([np.zeros((h, 1), np.uint8), pixels.reshape(h, w * c)], axis=1)
+
+  def chunk(tag, data):
+    return struct.pack('>I', len(data)) + tag + data + struct.pack('>I', zlib.crc32(tag + data))
+
+  ihdr = struct.pack('>IIBBBBB', w, h, 8, 0 if c == 1 else 2, 0, 0, 0)
+  return (b'\x89PNG\r\n\x1a\n' + chunk(b'IHDR', ihdr) +
+          chunk(b'IDAT', zlib.compress(rows.tobytes(), 6)) + chunk(b'IEND', b''))
+
+
+def _to_uint8(x: torch.Tensor) -> np.ndarray:
+  """tf.image.convert_image_dtype(float -> uint8) on the host: x * 255.5, saturated, truncated."""
+  return np.clip(x.detach().float().cpu().numpy() * np.float32(255.5), 0, 255).astype(np.uint8)
+
+
 @gin.configurable(denylist=['strategy', 'model_dir'])
 class GANManager(abc.ABC):
   """Constructor surface of the reference (:98-167)."""
@@ -361,6 +387,118 @@ class GANManager(abc.ABC):
                                                 predict_depth=self.predict_depth,
                                                 unproject_void_class=0)
     return res
+
+  def _score_file(self):
+    return os.path.join(self.model_dir, f'scores_{self.test_split}.csv')
+
+  def _unevaluated_checkpoints(self):
+    """Every ckpt-<step>.npz under model_dir without a row in the score file, in step order (the
+    reference's task_manager.unevaluated_checkpoints, :80-141, without the polling and the wait)."""
+    done = set()   # absolute: model_dir may be given relative in one run and absolute in the next
+    if os.path.exists(self._score_file()):
+      with open(self._score_file(), newline='') as f:
+        done = {os.path.abspath(r['checkpoint_path']) for r in csv.DictReader(f)}
+    found = []
+    for name in os.listdir(self.model_dir):
+      m = re.fullmatch(r'ckpt-(\d+)\.npz', name)
+      path = os.path.join(self.model_dir, name)
+      if m and os.path.abspath(path) not in done:
+        found.append((int(m.group(1)), path))
+    return [path for _, path in sorted(found)]
+
+  @staticmethod
+  def _checkpoint_step(checkpoint_path):
+    """The number that ends a checkpoint's name ('ckpt-2000.npz', 'test-1'), as the reference's
+    add_eval_result takes it (utils/task_manager.py:171)."""
+    name = os.path.basename(checkpoint_path)
+    m = re.fullmatch(r'.*-(\d+)(\.npz)?', name)
+    if not m:
+      raise ValueError(f"checkpoint name {name!r} does not end in '-<step>' or '-<step>.npz': "
+                       'its row in the score file needs the step')
+    return int(m.group(1))
+
+  def _add_eval_result(self, checkpoint_path, step, result_dict):
+    """One row of scores_<split>.csv (reference utils/task_manager.py:166-187): checkpoint_path,
+    step, then the sorted result keys, floats as '{:.3f}'."""
+    header = ['checkpoint_path', 'step'] + sorted(result_dict)
+    row = dict(checkpoint_path=checkpoint_path, step=str(step))
+    row.update({k: '{:.3f}'.format(float(v)) for k, v in result_dict.items()})
+    new = not os.path.exists(self._score_file())
+    if not new:
+      with open(self._score_file(), newline='') as f:
+        have = next(csv.reader(f), None)
+      if have != header:   # e.g. another eval_seq_len: columns would be dropped or left blank
+        raise ValueError(f'{self._score_file()} has the columns {have}, this run writes {header}')
+    with open(self._score_file(), 'a', newline='') as f:
+      writer = csv.DictWriter(f, fieldnames=header)
+      if new:
+        writer.writeheader()
+      writer.writerow(row)
+    return row
+
+  def _save_rollout_images(self, rollout, step):
+    """images/<split>/<step>/<frame>/<example>_{rgb,depth}.png of the EMA roll-out (:274-296)."""
+    root = os.path.join(self.model_dir, 'images', self.test_split, str(step))
+    for suffix, frames in (('rgb', rollout.generated), ('depth', rollout.pred_depth)):
+      for frame_idx, frame in enumerate(frames):
+        frame_dir = os.path.join(root, str(frame_idx))
+        os.makedirs(frame_dir, exist_ok=True)
+        pixels = _to_uint8(frame)
+        for example_idx in range(pixels.shape[0]):
+          with open(os.path.join(frame_dir, f'{example_idx}_{suffix}.png'), 'wb') as f:
+            f.write(_encode_png(pixels[example_idx]))
+
+  def test(self, eval_examples=None, checkpoints=None, unit_test: bool = False, inception=None):
+    """The evaluation loop of the reference (:233-322) minus TensorBoard and the polling task
+    manager.  eval_examples: parsed trajectory examples (what R2RVideoDataset.input_fn takes: a
+    sequence of per-example dicts, or a callable returning a fresh iterator); TFRecord parsing
+    stays outside.  checkpoints: .npz paths (save_checkpoint files); None: every ckpt-<step>.npz
+    under model_dir that has no row in scores_<test_split>.csv yet, in step order.  unit_test:
+    one pass over the randomly initialised model under the checkpoint name 'test-1'.
+
+    Per checkpoint: restore, roll the display batch out (_get_image_grid), write the EMA
+    roll-out's frames as PNG, FID / RMSE per frame index for the generator and its EMA, one CSV
+    row.  The step of a row (and of its image directory) is the number that ends the checkpoint's
+    name.  Returns the rows written."""
+    from se3ds_amd.datasets import indoor_datasets
+    from se3ds_amd.utils import eval_metric
+    if self.strategy.num_replicas_in_sync != 1:
+      raise NotImplementedError('EvalMetric runs on one device; merge FeatureMoments across ranks')
+    if eval_examples is None:
+      raise ValueError('no evaluation data: pass eval_examples (parsed trajectory examples)')
+    if unit_test:
+      checkpoints = ['test-1']
+    elif checkpoints is None:
+      checkpoints = self._unevaluated_checkpoints()
+    steps = [self._checkpoint_step(c) for c in checkpoints]   # a bad name fails before any work
+    self.global_batch_size = self.test_batch_size
+    dataset = indoor_datasets.R2RVideoDataset()   # gin supplies its arguments
+    dev = self.strategy.device
+    self.eval_ds = dataset.input_fn(eval_examples, self.test_batch_size, seed=self.seed, device=dev)
+    # a second, independent stream over the same examples (reference :214-225)
+    self.display_batch = next(dataset.input_fn(eval_examples, self.test_batch_size, seed=self.seed,
+                                               device=dev))
+    self.eval_num = (len(eval_examples) if hasattr(eval_examples, '__len__')
+                     else dataset.num_examples[self.test_split])
+    metric = eval_metric.EvalMetric(ds=self.eval_ds, eval_num=self.eval_size or self.eval_num,
+                                    batch_size=self.test_batch_size, strategy=None, avg_num=1,
+                                    eval_seq_len=self.eval_seq_len, inception=inception)
+    if not hasattr(self, 'generator'):
+      self._create_obj()
+    rows = []
+    for checkpoint_path, step in zip(checkpoints, steps):
+      if not unit_test:
+        self.restore_checkpoint(checkpoint_path)
+      self._save_rollout_images(self._get_image_grid(self.display_batch, modes=('ema',))['ema'],
+                                step)
+      fid, _, rmse = metric.calculate_fid_score(self.generator)
+      ema_fid, _, ema_rmse = metric.calculate_fid_score(self.ema_generator)
+      result = {}
+      for i in fid:
+        for k, v in (('fid', fid), ('ema_fid', ema_fid), ('rmse', rmse), ('ema_rmse', ema_rmse)):
+          result[f'{self.test_split}/eval_image/{k}@{i}'] = v[i]
+      rows.append(self._add_eval_result(checkpoint_path, step, result))
+    return rows
 
   # -------------------------------------------------------------------------- checkpoint
   # The reference keeps tf.train.Checkpoint(generator, discriminator, ema_generator, g_optimizer,

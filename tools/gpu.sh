@@ -16,6 +16,7 @@
 #   pmc_step TAG [ENV=v ...]    MFMA-busy + shader clock of every kernel inside the step (1 pass, tools/pmc_step.py)
 #   prof_py TAG <file.py> [args] rocprofv3 kernel stats of any python tool -> $OUT/TAG_kernel_stats.csv
 #   pmc_py TAG "PMC ..." REGEX <file.py> [args]   one --pmc pass over any python tool -> $OUT/TAG_pmc.json
+#   video_input [args]          tools/video_input_bench.py (fused evaluation input transform vs op by op) -> $OUT/video_input_bench.json
 #   py <file.py> [args]         any python tool
 cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
@@ -140,6 +141,10 @@ for k, v in d.items():
   print(k[:60], ' '.join('%s=%.4g' % (a, (b['avg'] if isinstance(b, dict) and 'avg' in b else b)) for a, b in v.items() if not isinstance(b, dict) or 'avg' in b))
 PY
   rm -rf $OUT/pmc_tmp_g
+}
+task_video_input() {
+  timeout 600 python tools/video_input_bench.py --out $OUT/video_input_bench.json "$@" > $OUT/video_input_bench.log 2>&1
+  echo "video_input rc=$?"; grep -v '^{' $OUT/video_input_bench.log | tail -9 | cut -c1-300
 }
 task_py() { timeout 1500 python "$@"; }
 args=()
