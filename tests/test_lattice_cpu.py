@@ -277,3 +277,214 @@ def test_duplicated_split_slab_and_shifted_ragged_tile_are_flagged():
   flat[-5:] = y.reshape(-1, y.shape[3])[-6:-1]      # the ragged last tile written one pixel late
   r = LT.mismatch_report(shifted, y)
   assert r is not None and 'by n: 1' in r
+
+
+# =============================================================================================
+# Optimiser, spectral and loss references: order independence on the lattice (float64 sum ==
+# fp32 accumulation in a shuffled order, bit for bit) and agreement with the independent
+# restatements of oracle/nets_torch.py on random data.
+
+def _same_bits(a, b):
+  return np.array_equal(np.asarray(a, np.float32).view(np.uint32), np.asarray(b, np.float32).view(np.uint32))
+
+
+@pytest.mark.parametrize('n', [1, 3, 4, 65535, 65537, 2 * 65536 + 5, 3 * 3 * 256 * 512])
+def test_sqnorm_and_clip_are_order_independent(n):
+  g = LT.pow4_gradient(n, 11 + n, scale=0.5)
+  sq = LT.sqnorm(g, 0.5)
+  assert LT.is_pow4(sq * 4)
+  for seed in (0, 1):
+    assert _same_bits(LT.shuffled_f32_sum(g * g, seed), LT.f32(sq))
+  assert _same_bits(np.sum((g * g).astype(np.float32), dtype=np.float32), LT.f32(sq))   # pairwise
+  norm = np.sqrt(sq)
+  assert norm == float(LT.f32(norm))
+  for clip in (norm / 4, norm * 4, 5.0):      # active, inactive, the trainer's value
+    out = LT.clip_by_norm(g, clip, sq)
+    want = (g * clip) / max(norm, clip)       # tf.clip_by_norm in float64
+    if clip == 5.0:
+      assert _same_bits(out, LT.f32(want))    # rounded once
+    else:
+      assert np.array_equal(out.astype(np.float64), want)   # exact: nothing rounds at all
+  assert not LT.pow4_gradient(n, 3, zero=True).any()
+  assert _same_bits(LT.clip_by_norm(np.zeros(n), 5.0), np.zeros(n))
+
+
+def test_clip_by_norm_agrees_with_the_oracle():
+  g = torch.randn(1000, dtype=torch.float64, generator=torch.Generator().manual_seed(0))
+  gl = torch.from_numpy(LT.pow4_gradient(1000, 5))
+  for clip in (0.5, 5.0, 64.0):
+    assert torch.equal(torch.from_numpy(LT.clip_by_norm(gl.numpy(), clip)).double(),
+                       O.clip_by_norm(gl, clip).float().double())
+  # random data: the reference formula itself (no lattice precondition) against the oracle
+  for clip in (0.5, 50.0):
+    want = O.clip_by_norm(g, clip).numpy()
+    got = (g.numpy() * clip) / max(np.sqrt((g.numpy() ** 2).sum()), clip)
+    assert rel_err(got, want) < 1e-15
+  sqs = [0.0, 1.0, 16.0, 64.0, 4.0 ** 6]
+  want = np.mean([np.sqrt(s) * 5.0 / max(np.sqrt(s), 5.0) for s in sqs])
+  assert float(LT.mean_clipped_norm(sqs, 5.0)) == float(np.float32(want))
+  assert float(LT.mean_clipped_norm([0.0, 0.0], 5.0)) == 0.0
+
+
+SN_CPU = [(27, 1, 1.0, 3), (288, 3, 0.5, -5), (2048, 256, 2.0, 7), (1152, 1024, 0.5, 1)]
+
+
+@pytest.mark.parametrize('K,C,inv,dot', SN_CPU)
+def test_sn_fixup_is_order_independent(K, C, inv, dot):
+  s = LT.sn_case(K, C, K + C, inv, dot, density=0.25)
+  out, r = LT.sn_fixup(**s)
+  assert r['dot'] == dot
+  vu = np.outer(s['v'], s['uhat'])
+  for key, terms in (('dot', s['G'] * s['W']), ('gg', s['G'] ** 2), ('gvu', s['G'] * vu),
+                     ('nv', s['v'] ** 2), ('nu', s['uhat'] ** 2)):
+    assert _same_bits(LT.shuffled_f32_sum(terms, 7), LT.f32(r[key])), key
+  # the fix-up in plain fp32 arithmetic and the squared norm of its result, any order
+  G32, v32, u32 = (s[k].astype(np.float32) for k in ('G', 'v', 'uhat'))
+  coef = np.float32(inv) * np.float32(inv) * np.float32(r['dot'])
+  fix32 = np.float32(inv) * G32 - coef * v32[:, None] * u32[None, :]
+  assert _same_bits(fix32, LT.f32(out))
+  if r['sq'] / r['quantum'] ** 2 < LT.LIMIT:
+    assert _same_bits(LT.shuffled_f32_sum(fix32 * fix32, 9), LT.f32(r['sq']))
+  # against autograd through sigma = v W u^T of W / sigma (float64)
+  W = torch.from_numpy(s['W']).requires_grad_(True)
+  v, u = torch.from_numpy(s['v']), torch.from_numpy(s['uhat'])
+  sigma = 1.0 / inv
+  # d/dW of f(W * inv(W)) with inv = 1 / sigma(W), d sigma / dW = v u^T, evaluated where sigma(W)
+  # has the table's value: inv * G - inv^2 <G, W> v u^T
+  sig = (v @ W @ u)
+  sig_here = sig.detach()
+  weff = W / (sig - sig_here + sigma)
+  (weff * torch.from_numpy(s['G'])).sum().backward()
+  assert rel_err(out, W.grad.numpy()) < 1e-13
+
+
+@pytest.mark.parametrize('K,C', [(27, 1), (64, 128), (1152, 3), (2048, 512)])
+def test_power_iteration_agrees_with_the_oracle(K, C):
+  g = torch.Generator().manual_seed(K * 7 + C)
+  W = torch.randn(K, C, dtype=torch.float64, generator=g)
+  u = torch.randn(1, C, dtype=torch.float64, generator=g)
+  sigma, uhat = O.power_iteration(W.reshape(1, 1, K, C), u)
+  r = LT.power_iteration(W.numpy(), u.numpy())
+  assert rel_err(r['uhat'], uhat.numpy().reshape(-1)) < 1e-12
+  assert abs(float(r['sigma']) - float(sigma)) < 1e-12 * abs(float(sigma))
+  r32 = LT.power_iteration(W.numpy(), u.numpy(), np.float32)
+  floor = max(LT.scaled_err(r32[k], r[k]) for k in ('v', 'uhat', 'sigma', 'inv'))
+  assert 0 < floor < 1e-5, floor
+
+
+def _adam_inputs(n, seed):
+  r = LT.rng(seed)
+  p = LT.f32(r.standard_normal(n) * 0.05)
+  g = LT.clip_by_norm(LT.pow4_gradient(n, seed + 1), 5.0)
+  m = LT.f32(r.standard_normal(n) * 0.1)
+  v = LT.f32(r.random(n) * 0.02)
+  e = LT.f32(p + r.standard_normal(n) * 0.01)
+  return p, g, m, v, e
+
+
+@pytest.mark.parametrize('step', [1, 2, 1000])
+def test_adam_and_ema_references(step):
+  """Worst ratio of |fp32 NumPy - float64| to the bound K * 2^-24 * (largest intermediate), on
+  these inputs (n = 200000, seed 3): m' 0.20, v' 0.20, p' 0.07, e' 0.06 at every step -- a
+  plain fp32 evaluation of the documented formulas sits well inside the bound (the kernels on
+  an MI355X: 0.25, 0.20, 0.07, 0.06, tests/test_optim_lattice_gpu.py)."""
+  p, g, m, v, e = _adam_inputs(200000, 3)
+  lr, b1, b2, eps, omd = 1e-4, 0.5, 0.999, 1e-7, np.float32(1.0 - 0.999)
+  # against the oracle on the same inputs (float64 tensors, its own alpha)
+  t = lambda a: torch.from_numpy(a.astype(np.float64))
+  po, mo, vo = O.adam_keras(t(p), t(g), t(m), t(v), float(np.float32(lr)), float(np.float32(b1)),
+                            float(np.float32(b2)), step, float(np.float32(eps)))
+  p2, m2, v2, mag = LT.adam_keras(p, g, m, v, lr, b1, b2, step, eps)
+  assert rel_err(m2, mo.numpy()) < 1e-14 and rel_err(v2, vo.numpy()) < 1e-14
+  assert rel_err(p2, po.numpy()) < 1e-6      # alpha: fp32 operations here, float64 there
+  a64 = float(np.float32(lr)) * np.sqrt(1 - float(np.float32(b2)) ** step) / (1 - float(np.float32(b1)) ** step)
+  # fp32(b^t) is off by up to half an ulp of a number below 1; 1 - b^t then cancels
+  b1t, b2t = float(np.float32(b1)) ** step, float(np.float32(b2)) ** step
+  tol = (4 + 0.25 / (1 - b2t) + 0.5 / (1 - b1t)) * LT.ULP
+  assert abs(float(LT.adam_alpha(lr, b1, b2, step)) - a64) < tol * a64
+  e2, mage = LT.ema(e, p2, omd)
+  eo = O.ema_step({'x': t(e)}, {'x': torch.from_numpy(p2)}, 10, float(omd) * -1 + 1, 0, 5)['x']
+  assert rel_err(e2, eo.numpy()) < 1e-9      # the oracle takes 1 - decay in float64
+  # plain fp32 evaluation of the same formulas stays inside the bound
+  p3, m3, v3, _ = LT.adam_keras(p, g, m, v, lr, b1, b2, step, eps, np.float32)
+  e3, _ = LT.ema(e, p3, omd, np.float32)
+  ratios = dict(m=LT.bound_ratio(m3, m2, LT.K_M, mag['m']), v=LT.bound_ratio(v3, v2, LT.K_V, mag['v']),
+                p=LT.bound_ratio(p3, p2, LT.K_P, mag['p']),
+                e=LT.bound_ratio(e3, e2, LT.K_P + LT.K_E, np.maximum(mage, mag['p'])))
+  print(f'step {step}: fp32 NumPy / bound: ' + ' '.join(f'{k}={x:.3f}' for k, x in ratios.items()))
+  assert max(ratios.values()) <= 1.0, ratios
+
+
+def test_hinge_reference_is_order_independent():
+  for half in (1, 255, 257, 8 * 30 * 62):
+    x = LT.pick((2 * max(half, 5),), half, LT.LOGIT_VALUES)[:2 * half] if half > 4 else np.array([-1.0, 1.0])
+    if half > 4:
+      x[half:half + 9] = LT.LOGIT_VALUES
+    sums, dd, dg = LT.hinge(x, 0.5, 0.25)
+    f, r = x[:half], x[half:]
+    assert _same_bits(LT.shuffled_f32_sum(-f, 1), sums[0])
+    assert _same_bits(LT.shuffled_f32_sum(np.maximum(1 - r, 0) + np.maximum(1 + f, 0), 2), sums[1])
+    # against autograd of the oracle's terms
+    t = torch.from_numpy(x).requires_grad_(True)
+    disc = (F.relu(1.0 - t[half:]) + F.relu(1.0 + t[:half])).sum()
+    disc.backward()
+    # relu'(0) = 0 in torch as in the kernels' strict comparison: logits at exactly +-1
+    assert np.array_equal(dd.astype(np.float64), 0.5 * t.grad.numpy())
+    assert np.array_equal(dg[:half], np.full(half, -0.25, np.float32)) and not dg[half:].any()
+    assert float(sums[1]) == float(disc.detach())
+
+
+@pytest.mark.parametrize('mode', [0, 1, 2, 3, 4])
+def test_sample_sum_reference_is_order_independent(mode):
+  n, p, c = 2, 8191, 3 if mode != 3 else 1
+  vals = LT.COARSE_DEPTHS if mode == 4 else LT.DEPTH_VALUES
+  a, b = LT.pick((n, p, c), 1, vals), LT.pick((n, p, c), 2, vals)
+  if mode == 3:   # the trainer's masks: m in {0, 1}, blurred m2 on the lattice of 1/2
+    a, b = LT.pick((n, p, c), 1, (0.0, 1.0)), LT.pick((n, p, c), 2, (0.0, 0.5, 1.0))
+  m = LT.pick((n, p), 3, (0.0, 1.0))
+  out = LT.sample_sum(a, b, m, mode)
+  terms = {0: a, 1: np.abs(a - b) * m[..., None], 2: (a > 0) & (a < 1), 3: a * (1 - b),
+           4: (a - b) ** 2 * ((b > 0) & (b < 1))}[mode].astype(np.float64).reshape(n, -1)
+  for i in range(n):
+    assert _same_bits(LT.shuffled_f32_sum(terms[i], i), out[i])
+  if mode == 1:   # the oracle's wc_loss is this sum / c / max(sum(mask), 1)
+    msum = LT.sample_sum(m[..., None], None, None, 0)
+    wc = out.astype(np.float64) / c / np.maximum(msum, 1)
+    ref = O.wc_loss(torch.from_numpy(a).reshape(n, 1, p, c), torch.from_numpy(b).reshape(n, 1, p, c),
+                    torch.from_numpy(m).reshape(n, 1, p, 1)).numpy()
+    assert rel_err(wc, ref) < 1e-15
+
+
+@pytest.mark.parametrize('mode', [0, 1, 2, 3])
+def test_l1_grad_reference(mode):
+  n, p, c = 3, 1000, 3
+  a, b = LT.pick((n, p, c), 1, LT.DEPTH_VALUES), LT.pick((n, p, c), 2, LT.DEPTH_VALUES)
+  m, m2 = LT.pick((n, p), 3, (0.0, 1.0)), LT.pick((n, p), 4, (0.0, 0.5, 1.0))
+  coef = np.array([0.5, 2.0, 0.125])
+  got = LT.l1_grad(a, b, m, m2, coef, mode).astype(np.float64)
+  ta = torch.from_numpy(a).requires_grad_(True)
+  tb = torch.from_numpy(b)
+  w = ((tb > 0) & (tb < 1)).double() if mode in (0, 2) else (torch.from_numpy(m * (1 - m2))[..., None]).expand(n, p, c)
+  if mode >= 2:
+    assert np.array_equal(got, w.numpy())
+    return
+  ((ta - tb).abs() * w * torch.from_numpy(coef).reshape(n, 1, 1)).sum().backward()
+  assert np.array_equal(got, ta.grad.numpy())     # torch: d|x|/dx = sign(x), 0 at 0
+  assert (got == 0).any() and (got > 0).any() and (got < 0).any()
+
+
+def test_recip_clamp_and_head_references():
+  s = np.array([0.0, 0.5, 1.0, 3.0, 8191.0, 1572864.0])
+  got = LT.recip_clamp(s, 100.0)
+  assert _same_bits(got, (np.float32(100.0) / np.maximum(s.astype(np.float32), np.float32(1))))
+  x = LT.pick((1000,), 1, (-0.5, 0.0, 0.25, 1.0, 1.5))
+  y = LT.head_fwd(x, 1)
+  assert np.array_equal(y, np.clip(x, 0, 1))
+  dy = LT.pick((1000,), 2, (0.5, 1.0, -2.0))
+  assert np.array_equal(LT.head_bwd(dy, y, x, 1), np.where((x >= 0) & (x <= 1), dy, 0))
+  xr = LT.rng(0).standard_normal(1000) * 2
+  t = torch.from_numpy(xr).requires_grad_(True)
+  yo = (torch.tanh(t) + 1) / 2
+  yo.backward(torch.from_numpy(dy))
+  assert rel_err(LT.head_fwd(xr, 0), yo.detach().numpy()) < 1e-15
+  assert rel_err(LT.head_bwd(dy, LT.head_fwd(xr, 0), xr, 0), t.grad.numpy()) < 1e-12
