@@ -679,6 +679,28 @@ int se3ds_video_transform(const float* image, const uint8_t* segmentation,
                           uint8_t* o_pd_seg, float* o_depth, float* o_pd_depth, void* stream);
 
 /* ======================================================================================
+ * VLN perturbation augmentation -- inference/perturbation_utils.py:63-70.  csrc/perturb.hip.
+ * ====================================================================================== */
+
+/* The collision screen for k candidate offsets in one launch: count[c] = number of pixels (r, x)
+ * of image image_index[c] (NULL: image 0) of depth fp32 (n, height, width) with
+ * row0 <= r < row1, col0 <= x < col1 and depth * depth_scale < threshold[c] -- one fp32 multiply,
+ * one strict compare, a NaN never counts.  windows int32 (k, 4) = row0, row1, col0, col1;
+ * threshold fp32 (k); all device pointers.  count int32 (k) is zeroed by the call itself (a memset
+ * node on `stream`), the caller pre-fills nothing.  An empty window is legal and counts 0.
+ * Deterministic (integer sums).  BADSHAPE for n, height, width or k < 1, k > 65535 or
+ * height * width > INT32_MAX.  The window table is validated on the host, by
+ * se3ds_collision_check_windows on the copy the caller made it from; the kernel clamps what it
+ * gets to the image, so a bad table cannot make it read outside `depth`. */
+int se3ds_collision_count(const float* depth, int n, int height, int width, const int32_t* windows,
+                          const int32_t* image_index, const float* threshold, float depth_scale,
+                          int k, int32_t* count, void* stream);
+/* HOST pointers, no device work: BADSHAPE if a window leaves [0, height] x [0, width], has
+ * row0 > row1 or col0 > col1, or an image index (NULL: none) lies outside [0, n). */
+int se3ds_collision_check_windows(const int32_t* windows, const int32_t* image_index, int n,
+                                  int height, int width, int k);
+
+/* ======================================================================================
  * Inception-v3 evaluator -- utils/inception_utils.py, utils/eval_metric.py EvalMetric
  * (reference utils/inception_utils.py, utils/eval_metric.py:66-343).  csrc/inception.hip.
  * ====================================================================================== */

@@ -247,3 +247,56 @@ class SE3DSModel(object):
                       pred_rgb=pred_rgb,
                       proj_depth=proj_depth, pred_depth=pred_depth, mu=mu, logvar=logvar,
                       proj_mask=proj_mask)
+
+  def predict_views(self, positions) -> OutputData:
+    """Renders B views of the current memory with ONE generator forward: `positions` (B, 3).  Each
+    view is projected by the batch-1 warp exactly as `__call__` does it (the memory is a batch-1
+    point cloud), the B projections are concatenated, the generator runs once at batch B with
+    training=False, and the outputs are quantised as in `__call__` (reference :247-331 per view).
+    Nothing is added to the memory and `prev_rgb_frame` is left alone: this is the
+    add_preds_to_memory=False path for many positions at once (inference.perturbation_augment).
+    The generator is ~5.75 TFLOP per panorama and the warp tens of microseconds: the batch
+    dimension is what fills the device."""
+    if positions.ndim != 2 or positions.shape[1] != 3 or positions.shape[0] < 1:
+      raise ValueError(f'positions must be (B, 3) with B >= 1, got {tuple(positions.shape)}')
+    _lib.require_cuda(positions)
+    positions = positions.to(torch.float32)
+    views = positions.shape[0]
+    h, w = self.height, self.width
+    sem, rgb, dep, msk = [], [], [], []
+    for b in range(views):
+      position = positions[b:b + 1]
+      _, proj_semantic = pano_utils.project_feats_to_equirectangular(
+          self._memory.feats, self._memory.coords, h, w, constants.INVALID_SEM_VALUE,
+          self.depth_scale, offset=position)
+      proj_depth, proj_rgb, proj_mask = pano_utils.project_feats_to_equirectangular(
+          self._memory.rgb, self._memory.rgb_coords, h, w, constants.INVALID_RGB_VALUE,
+          self.depth_scale, offset=position, with_mask=True,
+          mask_void=constants.INVALID_RGB_VALUE)
+      sem.append(proj_semantic)
+      rgb.append(proj_rgb)
+      dep.append(proj_depth)
+      msk.append(proj_mask)
+    proj_semantic, proj_rgb = torch.cat(sem, dim=0), torch.cat(rgb, dim=0)
+    proj_depth, proj_mask = torch.cat(dep, dim=0), torch.cat(msk, dim=0)[..., None]
+    proj_semantic = _quantize(proj_semantic[..., 0], torch.uint8, lo=0, hi=255)
+    proj_rgb = _quantize(proj_rgb, torch.float32, div=255.0, lo=0.0, hi=1.0)
+    assert self.prev_rgb_frame is not None
+    inputs = {
+        'prev_image': self.prev_rgb_frame.expand(views, -1, -1, -1), 'proj_image': proj_rgb,
+        'proj_depth': proj_depth[..., None], 'proj_mask': proj_mask,
+        'blurred_mask': torch.zeros_like(proj_mask),
+        'dataset_type': torch.zeros((views,), dtype=torch.int32, device=self.device),
+    }
+    (mu, logvar, _, pred_depth, pred_semantic, _, generated_pred_rgb) = self.model(
+        inputs=[inputs, None], sample_noise=False, training=False)
+    pred_depth = _quantize(pred_depth[..., 0], torch.float32, lo=0.0, hi=1.0)
+    pred_rgb = _quantize(generated_pred_rgb, torch.int32, mul=255.0, lo=0, hi=255, pre=(0.0, 1.0))
+    pred_semantic = torch.zeros(pred_semantic.shape[:-1], dtype=torch.uint8, device=self.device)
+    pred_rgb = _quantize(pred_rgb, torch.uint8, lo=0, hi=255)
+    point_cloud_utils.check_promise(pred_rgb.device, wait=False)
+    return OutputData(proj_semantic=proj_semantic, pred_semantic=pred_semantic,
+                      proj_rgb=_quantize(proj_rgb, torch.uint8, mul=255.0, lo=0, hi=255),
+                      pred_rgb=pred_rgb,
+                      proj_depth=proj_depth, pred_depth=pred_depth, mu=mu, logvar=logvar,
+                      proj_mask=proj_mask)
