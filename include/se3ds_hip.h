@@ -678,6 +678,25 @@ int se3ds_video_transform(const float* image, const uint8_t* segmentation,
                           int h, int w, float* o_original, float* o_image, uint8_t* o_seg,
                           uint8_t* o_pd_seg, float* o_depth, float* o_pd_depth, void* stream);
 
+/* PNG reconstruction (un-filtering) of a whole batch in one launch -- the second half of
+ * tf.image.decode_png (datasets/indoor_datasets.py:185-228); the host inflates.  csrc/png.hip.
+ * src: the inflated streams of all images, one device buffer of src_bytes bytes; a stream is
+ * height x (1 filter-type byte + row_bytes filtered bytes).  table: device int64
+ * [n][se3ds_png_unfilter_fields() = 6] = source byte offset into src, destination device pointer
+ * (height x row_bytes bytes, dense), height, row_bytes, bytes per pixel (1, 2 or 3), 16-bit flag
+ * (0 / 1; with 2 bytes per pixel only: the two bytes of a sample are stored swapped, big-endian ->
+ * little-endian).  Images of different geometry and bytes per pixel share the launch, one wavefront
+ * each.  host_table: the HOST copy the device table was made from; it is validated here before
+ * anything runs (BADSHAPE: n < 1 or > 65535, a null destination, height < 1, row_bytes not a
+ * multiple of the bytes per pixel, a stream that leaves src; UNSUPPORTED: row_bytes above
+ * se3ds_png_unfilter_max_row_bytes()), the kernel reads only the device copy.  Filter types above 4
+ * are the caller's to reject (utils/png.py does); the kernel treats them as None.  Exact integer
+ * arithmetic, deterministic. */
+int se3ds_png_unfilter(const uint8_t* src, int64_t src_bytes, const int64_t* table,
+                       const int64_t* host_table, int n, void* stream);
+int se3ds_png_unfilter_fields(void);
+int se3ds_png_unfilter_max_row_bytes(void);
+
 /* ======================================================================================
  * VLN perturbation augmentation -- inference/perturbation_utils.py:63-70.  csrc/perturb.hip.
  * ====================================================================================== */

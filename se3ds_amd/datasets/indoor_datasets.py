@@ -1,8 +1,13 @@
 """Device-side half of the reference's datasets/indoor_datasets.py: `augment`
 (:34-61) and `R2RImageDataset`'s per-example transform (:263-375) + batch transform (:553-597) as
-ONE gather kernel over decoded frames resident in HBM (`se3ds_input_transform`).  TFRecord / PNG
-decoding, sharding, shuffling and prefetching stay outside: the caller hands over
-uint8 / uint16 frames (what `tf.image.decode_png` yields, :185-228) as CUDA tensors.
+ONE gather kernel over decoded frames resident in HBM (`se3ds_input_transform`), fed either by the
+caller (uint8 / uint16 frames, what `tf.image.decode_png` yields, :185-228, as CUDA tensors) or
+straight from the published TFRecord files: `R2RImageDataset._parse` (:125-247) reads a record with
+utils/tf_records.py, `input_fn` (datasets/base_dataset.py:105-150) lists, repeats, shuffles and
+batches them, and utils/png.py decodes the seven PNGs of every example -- inflate on a small host
+thread pool, reconstruction of the whole batch in one launch (`se3ds_png_unfilter`).  TensorFlow is
+not needed.  Not built: sharding over several input pipelines beyond the seed offset, `cache`, the
+RE10K records (`visible_mask`, `_transform_fn_re10k`).
 
 Same constructor arguments and gin selectors as the reference (`R2RImageDataset.image_size`, ...).
 The random draws follow the statement order of `_transform_fn` and are made on the host with a
@@ -12,7 +17,12 @@ downstream of the draws is bit-exact against oracle/input_np.py.
 `R2RVideoDataset` is the evaluation side (:604-827): the per-example transform of the trajectory
 records (`_transform_fn`, :734-792) over all N*T frames of a batch as one gather
 (`se3ds_video_transform`), and an `input_fn` that batches parsed examples the way the reference's
-tf.data pipeline does (repeat, then batch) and yields what `EvalMetric` consumes."""
+tf.data pipeline does (repeat, then batch) and yields what `EvalMetric` consumes;
+`examples_from_tfrecords` parses the trajectory records (:626-719) into those examples."""
+import concurrent.futures
+import enum
+import glob
+import os
 from typing import Callable, Dict, Iterable, Iterator, List, Optional, Sequence, Union
 
 import numpy as np
@@ -21,10 +31,35 @@ import torch
 from se3ds_amd import _lib
 from se3ds_amd import constants
 from se3ds_amd import gin_lite as gin
+from se3ds_amd.utils import png
+from se3ds_amd.utils import tf_records
+from se3ds_amd.utils.tf_records import FixedLenFeature
 
 F32 = np.float32
 RAW_DTYPES = dict(image=torch.uint8, proj_image=torch.uint8, depth=torch.int16, proj_depth=torch.int16,
                   proj_mask=torch.uint8, blurred_mask=torch.uint8, segmentation=torch.uint8)
+
+# plane -> (feature of the record, channels, bit depth) as `_parse` decodes it (:185-228)
+IMAGE_PLANES = dict(image=('image/encoded', 3, 8), proj_image=('proj/encoded', 3, 8),
+                    depth=('image/depth', 1, 16), proj_depth=('proj/depth', 1, 16),
+                    proj_mask=('proj/mask', 1, 8), blurred_mask=('image/blurred_mask', 1, 8),
+                    segmentation=('image/segmentation/class/encoded', 1, 8))
+
+
+class DatasetType(enum.Enum):
+  MP3D = 0
+  GIBSON = 1  # Unused
+  RE10K = 2
+
+
+def _record_files(file_pattern: str) -> List[str]:
+  """The sorted files of a pattern.  No match raises ValueError with the reference's message; the
+  reference raises it as AssertionError (`assert tf.io.gfile.glob(...)`, base_dataset.py:59), which
+  would vanish under `python -O`."""
+  files = sorted(glob.glob(file_pattern))
+  if not files:
+    raise ValueError(f'No data files matched {file_pattern}')
+  return files
 
 
 def draw_augment(rng: np.random.Generator, width: int, random_roll_range: Optional[int] = None,
@@ -139,6 +174,156 @@ class R2RImageDataset:
     n, h0, w0 = raw['proj_mask'].shape
     return self.device_transform(raw, [self.draw_params(rng, h0, w0) for _ in range(n)])
 
+  # --------------------------------------------------------------------------- TFRecord input
+  def _features(self) -> Dict[str, FixedLenFeature]:
+    """The feature spec of the reference's `_parse` (:149-178)."""
+    s = lambda: FixedLenFeature([], 'string', '')
+    return {
+        'scan_id': s(),
+        'dataset_type': FixedLenFeature([], 'int64', 0),
+        'depth_scale': FixedLenFeature([], 'float32', 10.0),
+        'image/encoded': s(), 'image/filename': s(), 'image/depth': s(), 'image/visible_mask': s(),
+        'image/blurred_mask': s(), 'image/segmentation/class/encoded': s(), 'proj/encoded': s(),
+        'proj/depth': s(), 'proj/mask': s(),
+        'bbox': FixedLenFeature([4], 'float32', [0.0, 0.0, 0.0, 0.0]),
+    }
+
+  def _parse(self, record: bytes) -> dict:
+    """One serialized tf.train.Example -> the host half of the reference's `_parse` (:125-247): the
+    seven planes of RAW_DTYPES as `png.PngPlane`s (container parsed, IDAT inflated, NOT yet
+    reconstructed -- `png.decode_png_batch` does that for a whole batch on the device), plus
+    dataset_type, depth_scale, bbox and, with return_filename, filename and scan_id.
+
+    A plane that is not (preprocessed_image_height, 2 * preprocessed_image_height) raises
+    ValueError, as `set_shape` does; so does one of another kind than the reference decodes it to
+    (RGB for the two images, 16-bit grey for the two depths, 8-bit grey for the rest: no channel
+    conversion is built).  `segmentation_valid` (:222-223) is left out: nothing in the reference's
+    trainer or here reads it.  Records of DatasetType.RE10K raise NotImplementedError
+    (`visible_mask` is not built)."""
+    ex = tf_records.apply_features(tf_records.parse_example(record), self._features())
+    if ex['dataset_type'] == DatasetType.RE10K.value:
+      raise NotImplementedError('RE10K records (visible_mask, _transform_fn_re10k) are not supported')
+    h, w = self.preprocessed_image_height, 2 * self.preprocessed_image_height
+    out = dict(dataset_type=np.int64(ex['dataset_type']))
+    for name, (feature, channels, depth) in IMAGE_PLANES.items():
+      try:
+        plane = png.parse_png(ex[feature])
+      except (ValueError, NotImplementedError) as e:
+        raise type(e)(f'{feature}: {e}') from None
+      if (plane.height, plane.width) != (h, w):
+        raise ValueError(f'{feature}: a {plane.height}x{plane.width} plane, the dataset is '
+                         f'preprocessed to {h}x{w}')
+      if (plane.channels, plane.bit_depth) != (channels, depth):
+        raise ValueError(f'{feature}: {plane.channels} channel(s) at bit depth {plane.bit_depth}, '
+                         f'expected {channels} at {depth}')
+      out[name] = plane
+    out['depth_scale'] = np.float32(ex['depth_scale'])
+    out['bbox'] = ex['bbox']
+    if self.return_filename:
+      out['filename'] = ex['image/filename']
+      out['scan_id'] = ex['scan_id']
+    return out
+
+  def get_file_patterns(self, split: Optional[str] = None, file_pattern: Optional[str] = None):
+    """The file pattern of a split (:249-261), with the reference's strings and errors."""
+    if not file_pattern:
+      if split not in ('train', 'val', 'val_unseen', 'val_seen', 'test'):
+        raise ValueError(f"Expected split to be one of ['train', 'val'], got {split}")
+      file_pattern = os.path.join(self.data_dir, f'{split}*.tfrecord')
+    return file_pattern
+
+  def _records(self, files: List[str], num_epochs: Optional[int], shuffle: bool,
+               shuffle_buffer_size: int, rng: np.random.Generator,
+               verify_crc: bool = False) -> Iterator[bytes]:
+    """files in order, records in file order, repeat, then tf.data's shuffle buffer: fill to
+    `shuffle_buffer_size`, then emit a uniformly drawn slot and refill it; drain at the end."""
+    def stream():
+      epoch = 0
+      while num_epochs is None or epoch < num_epochs:
+        seen = 0
+        for path in files:
+          for rec in tf_records.read_records(path, verify=verify_crc):
+            seen += 1
+            yield rec
+        if seen == 0:
+          raise ValueError(f'no records in {files}')
+        epoch += 1
+    if not shuffle:
+      yield from stream()
+      return
+    if shuffle_buffer_size < 1:
+      raise ValueError(f'shuffle_buffer_size {shuffle_buffer_size}')
+    buf = []
+    for rec in stream():
+      if len(buf) < shuffle_buffer_size:
+        buf.append(rec)
+        continue
+      i = int(rng.integers(len(buf)))
+      out, buf[i] = buf[i], rec
+      yield out
+    while buf:
+      yield buf.pop(int(rng.integers(len(buf))))
+
+  def input_fn(self, split: Optional[str] = None, batch_size: int = 1,
+               num_epochs: Optional[int] = None, shuffle: bool = False,
+               shuffle_buffer_size: int = 1000, file_pattern: Optional[str] = None, seed: int = 1,
+               input_pipeline_id: int = 0, device=None, decode_threads: int = 4,
+               verify_crc: bool = False) -> Iterator[Dict[str, torch.Tensor]]:
+    """Generator of step batches on the device, from TFRecord files: the dict `device_transform`
+    returns plus `depth_scale` fp32 (N,) (and, with return_filename, the host lists `filename` and
+    `scan_id`).  This is what GANManager.train(train_ds=...) takes.
+
+    The order is that of the reference's input_fn (datasets/base_dataset.py:105-150): files sorted,
+    records in file order, repeat(num_epochs), the shuffle buffer, batch with the remainder dropped
+    (batches run across the epoch boundary), decode, `draw_params` per example in batch order,
+    `device_transform`.  Two NumPy generators, both seeded seed + input_pipeline_id, make the
+    shuffle buffer's draws and the transform's draws (TensorFlow's streams cannot be reproduced).
+    The records of the NEXT batch are parsed and inflated on `decode_threads` workers (capped at
+    16) while the caller runs the current step; reconstruction is one launch per batch.
+
+    `verify_crc` is off by default: the record checksum is utils/tf_bundle.crc32c, a Python byte
+    loop of about 5 MB/s that holds the GIL, and a 512 x 1024 record of seven PNGs is in the MB
+    range -- a few hundred ms per record on the generator's own thread, where no prefetch hides it
+    and the inflate workers stall behind it.  Damage still surfaces: every PNG chunk carries a
+    CRC-32 that parse_png checks with zlib (C code), a broken protobuf or a wrong geometry raises,
+    and a lost record boundary ends in `truncated record`.  Switch it on to audit a file once."""
+    if batch_size <= 0:
+      raise ValueError(f'batch_size {batch_size}')
+    dev = torch.device(device if device is not None else f'cuda:{torch.cuda.current_device()}')
+    if dev.type != 'cuda':
+      raise _lib.Se3dsHipError(f'input_fn decodes and transforms on an MI355X (cuda) device; got {dev}.'
+                               '  There is no CPU fallback.')
+    files = _record_files(self.get_file_patterns(split, file_pattern))
+    local_seed = seed + input_pipeline_id
+    draw_rng = np.random.default_rng(local_seed)
+    records = self._records(files, num_epochs, shuffle, shuffle_buffer_size,
+                            np.random.default_rng(local_seed), verify_crc)
+    threads = max(1, min(int(decode_threads), png.MAX_THREADS))
+    h0, w0 = self.preprocessed_image_height, 2 * self.preprocessed_image_height
+
+    def submit(pool):
+      futures = []
+      for rec in records:
+        futures.append(pool.submit(self._parse, rec))
+        if len(futures) == batch_size:
+          return futures
+      return None   # the remainder is dropped
+
+    with concurrent.futures.ThreadPoolExecutor(max_workers=threads) as pool:
+      pending = submit(pool)
+      while pending is not None:
+        examples = [f.result() for f in pending]
+        pending = submit(pool)   # inflates under the step that consumes the batch below
+        raw = png.decode_png_batch({k: [e[k] for e in examples] for k in RAW_DTYPES}, dev, threads)
+        params = [self.draw_params(draw_rng, h0, w0) for _ in examples]
+        batch = self.device_transform(raw, params)
+        batch['depth_scale'] = torch.from_numpy(
+            np.array([e['depth_scale'] for e in examples], F32)).to(dev)
+        if self.return_filename:
+          batch['filename'] = [e['filename'] for e in examples]
+          batch['scan_id'] = [e['scan_id'] for e in examples]
+        yield batch
+
 
 VIDEO_PLANES = dict(segmentation=torch.uint8, pathdreamer_segmentation=torch.uint8,
                     depth=torch.float32, pathdreamer_depth=torch.float32)
@@ -150,8 +335,8 @@ VIDEO_PASS_THROUGH = ('id', 'mask', 'depth_scale', 'dataset_type', 'scan_id')
 class R2RVideoDataset:
   """Preprocessing of R2R trajectories for evaluation (reference :604-827).
 
-  TFRecord parsing stays outside: `raw` / `examples` hold what the reference's `_parse` (:626-719)
-  yields.  Not built: `one_hot_mask` of `_eval_transform_fn` (:797-801) -- no model in the reference
+  `raw` / `examples` hold what the reference's `_parse` (:626-719) yields; `examples_from_tfrecords`
+  makes them from the published files.  Not built: `one_hot_mask` of `_eval_transform_fn` (:797-801) -- no model in the reference
   or here reads it (the evaluator rebuilds its own, the image models ignore it) and at 512x1024 it is
   440 MB of fp32 per example -- and the `z` entry (the noise is drawn on the device, as for
   `R2RImageDataset`)."""
@@ -181,6 +366,72 @@ class R2RVideoDataset:
             f"Expected split to be one of ['train', 'val_seen', 'val_unseen'], got {split}")
       file_pattern = self.data_dir + f'{split}*.tfrecord'
     return file_pattern
+
+  # --------------------------------------------------------------------------- TFRecord input
+  def _features(self) -> Dict[str, FixedLenFeature]:
+    """The feature spec of the reference's `_parse` (:648-671), and the two `pathdreamer_*` planes
+    it reads as optional strings (older records lack them, VIDEO_OPTIONAL)."""
+    s = lambda: FixedLenFeature([], 'string', '')
+    return {
+        'id': FixedLenFeature([], 'int64', 0),
+        'scan_id': s(),
+        'dataset_type': FixedLenFeature([], 'int64', 0),
+        'depth_scale': FixedLenFeature([], 'float32', constants.DEPTH_SCALE),
+        'video/num_frames': FixedLenFeature([], 'int64'),
+        'video/rgb': s(), 'video/segmentations': s(), 'video/depth': s(), 'video/position': s(),
+        'video/mask': s(), 'video/pathdreamer_segmentations': s(), 'video/pathdreamer_depth': s(),
+    }
+
+  def _parse(self, record: bytes) -> Dict[str, np.ndarray]:
+    """One serialized trajectory Example -> the dict of NumPy arrays the reference's `_parse`
+    (:626-719) yields and `input_fn(examples=...)` takes: image fp32 (T,H0,W0,3), position fp32
+    (T,4), mask fp32 (T,), segmentation uint8 and depth fp32 (T,H0,W0), the two pathdreamer planes
+    when the record has them (segmentation stored int32, cast to uint8 as in :699-704), id,
+    dataset_type, depth_scale and, with return_filename, scan_id.  T = PANO_VIDEO_LENGTH; a plane
+    of another shape raises ValueError, as `ensure_shape` does."""
+    ex = tf_records.apply_features(tf_records.parse_example(record), self._features())
+    t = constants.PANO_VIDEO_LENGTH
+    shape = (t, self.preprocessed_image_height, 2 * self.preprocessed_image_height)
+    out = dict(id=np.int64(ex['id']), dataset_type=np.int64(ex['dataset_type']))
+
+    def tensor(feature, dtype, want):
+      a = tf_records.parse_tensor(ex[feature], dtype)
+      if a.shape != want:
+        raise ValueError(f'{feature}: shape {a.shape}, expected {want}')
+      return a
+    out['image'] = tensor('video/rgb', np.float32, shape + (3,))
+    out['position'] = tensor('video/position', np.float32, (t, 4))
+    out['mask'] = tensor('video/mask', np.float32, (t,))
+    out['segmentation'] = tensor('video/segmentations', np.uint8, shape)
+    if ex['video/pathdreamer_segmentations']:
+      out['pathdreamer_segmentation'] = tensor('video/pathdreamer_segmentations', np.int32,
+                                               shape).astype(np.uint8)
+    out['depth'] = tensor('video/depth', np.float32, shape)
+    if ex['video/pathdreamer_depth']:
+      out['pathdreamer_depth'] = tensor('video/pathdreamer_depth', np.float32, shape)
+    out['depth_scale'] = np.float32(ex['depth_scale'])
+    if self.return_filename:
+      out['scan_id'] = ex['scan_id']
+    return out
+
+  def examples_from_tfrecords(self, split: Optional[str] = None, file_pattern: Optional[str] = None,
+                              verify_crc: bool = False) -> Callable[[], Iterator[dict]]:
+    """The parsed examples of a split's TFRecord files (sorted, records in file order) as a
+    zero-argument callable that returns a fresh iterator -- what `input_fn(examples=...)` and
+    GANManager.test(eval_examples=...) take; one example is in memory at a time.
+
+    `verify_crc` is off by default, as in R2RImageDataset.input_fn and for the same reason, only
+    more so: a 512 x 1024 trajectory is roughly 100 MB of fp32, tens of seconds of the Python
+    CRC-32C per record.  Unlike the PNG planes, `tensor_content` carries no checksum of its own, so
+    with the default only the framing, the protobuf structure, the dtypes and the shapes are checked;
+    pass verify_crc=True to audit a file once."""
+    files = _record_files(self.get_file_patterns(split, file_pattern))
+
+    def examples():
+      for path in files:
+        for rec in tf_records.read_records(path, verify=verify_crc):
+          yield self._parse(rec)
+    return examples
 
   # ------------------------------------------------------------------------------ the draws
   def draw_params(self, rng: np.random.Generator) -> dict:

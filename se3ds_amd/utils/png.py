@@ -1,0 +1,178 @@
+"""PNG decoding without an imaging package: the container and the inflate on the host, the
+reconstruction (un-filtering) of every plane of a batch on the device in one launch
+(`se3ds_png_unfilter`, csrc/png.hip).  This is tf.image.decode_png as the reference's
+`R2RImageDataset._parse` uses it (datasets/indoor_datasets.py:185-228): 8-bit RGB, 8-bit grey and
+16-bit grey, non-interlaced.  Written from the PNG specification (ISO/IEC 15948, sections 5, 9, 11).
+There is no CPU fallback for the reconstruction."""
+import concurrent.futures
+import struct
+import zlib
+from typing import Dict, NamedTuple, Sequence, Union
+
+import numpy as np
+import torch
+
+from se3ds_amd import _lib
+
+SIGNATURE = b'\x89PNG\r\n\x1a\n'
+MAX_THREADS = 16
+_COLOUR_KINDS = {0: 'greyscale', 2: 'truecolour', 3: 'palette', 4: 'greyscale with alpha',
+                 6: 'truecolour with alpha'}
+_VALID_DEPTHS = {0: (1, 2, 4, 8, 16), 2: (8, 16), 3: (1, 2, 4, 8), 4: (8, 16), 6: (8, 16)}
+
+
+class PngPlane(NamedTuple):
+  """A parsed and inflated, not yet reconstructed PNG: `filtered` holds height scan lines of one
+  filter-type byte + width * channels * bit_depth / 8 filtered bytes."""
+  height: int
+  width: int
+  bit_depth: int
+  channels: int
+  filtered: bytes
+
+  @property
+  def bytes_per_pixel(self):
+    return self.channels * self.bit_depth // 8
+
+  @property
+  def row_bytes(self):
+    return self.width * self.bytes_per_pixel
+
+
+def parse_png(buf: bytes) -> PngPlane:
+  """Signature, chunk walk with CRC check, IHDR, the concatenated IDAT chunks inflated.  Supported:
+  colour type 0 at bit depth 8 or 16 and colour type 2 at bit depth 8, non-interlaced; any other
+  legal kind raises NotImplementedError naming it, every malformed input ValueError -- including a
+  filter-type byte above 4, so that the kernel never sees one."""
+  buf = bytes(buf)
+  if buf[:8] != SIGNATURE:
+    raise ValueError('not a PNG: bad signature')
+  pos, ihdr, idat, ended = 8, None, [], False
+  while pos < len(buf):
+    if len(buf) - pos < 12:
+      raise ValueError(f'PNG: truncated chunk header at offset {pos}')
+    length, = struct.unpack_from('>I', buf, pos)
+    tag = buf[pos + 4:pos + 8]
+    if len(buf) - pos - 12 < length:
+      raise ValueError(f'PNG: truncated {tag!r} chunk at offset {pos}')
+    data = buf[pos + 8:pos + 8 + length]
+    crc, = struct.unpack_from('>I', buf, pos + 8 + length)
+    if zlib.crc32(tag + data) != crc:
+      raise ValueError(f'PNG: CRC mismatch in the {tag!r} chunk at offset {pos}')
+    pos += 12 + length
+    if ihdr is None and tag != b'IHDR':
+      raise ValueError(f'PNG: first chunk is {tag!r}, not IHDR')
+    if tag == b'IHDR':
+      if ihdr is not None or length != 13:
+        raise ValueError('PNG: bad IHDR')
+      ihdr = struct.unpack('>IIBBBBB', data)
+    elif tag == b'IDAT':
+      idat.append(data)
+    elif tag == b'IEND':
+      ended = True
+      break
+    elif not tag[0] & 0x20:   # an upper-case first letter marks a critical chunk
+      if tag == b'PLTE':
+        continue              # the colour type decides below
+      raise ValueError(f'PNG: unknown critical chunk {tag!r}')
+  if ihdr is None:
+    raise ValueError('PNG: no IHDR chunk')
+  if not ended:
+    raise ValueError('PNG: no IEND chunk')
+  width, height, depth, colour, compression, filter_method, interlace = ihdr
+  if width == 0 or height == 0:
+    raise ValueError(f'PNG: {width} x {height} image')
+  if colour not in _COLOUR_KINDS or depth not in _VALID_DEPTHS[colour]:
+    raise ValueError(f'PNG: colour type {colour} at bit depth {depth} is not a PNG kind')
+  if compression != 0 or filter_method != 0 or interlace not in (0, 1):
+    raise ValueError(f'PNG: compression {compression}, filter method {filter_method}, '
+                     f'interlace {interlace}')
+  kind = f'{_COLOUR_KINDS[colour]} at bit depth {depth}'
+  if interlace:
+    raise NotImplementedError(f'PNG kind not supported: interlaced (Adam7) {kind}')
+  if (colour, depth) not in ((0, 8), (0, 16), (2, 8)):
+    raise NotImplementedError(f'PNG kind not supported: {kind}')
+  if not idat:
+    raise ValueError('PNG: no IDAT chunk')
+  channels = 3 if colour == 2 else 1
+  row_bytes = width * channels * depth // 8
+  try:
+    filtered = zlib.decompress(b''.join(idat))
+  except zlib.error as e:
+    raise ValueError(f'PNG: the IDAT stream does not inflate: {e}') from None
+  if len(filtered) != height * (1 + row_bytes):
+    raise ValueError(f'PNG: {len(filtered)} inflated bytes, {height} x (1 + {row_bytes}) expected')
+  types = np.frombuffer(filtered, np.uint8)[::1 + row_bytes]
+  if int(types.max()) > 4:
+    raise ValueError(f'PNG: filter type {int(types.max())} in row {int(np.argmax(types > 4))}')
+  return PngPlane(height, width, depth, channels, filtered)
+
+
+def _as_plane(item: Union[bytes, PngPlane]) -> PngPlane:
+  return item if isinstance(item, PngPlane) else parse_png(item)
+
+
+def decode_png_batch(bufs_by_key: Dict[str, Sequence[Union[bytes, PngPlane]]], device,
+                     threads: int = 4) -> Dict[str, torch.Tensor]:
+  """{key: the N PNGs of one plane of a batch} -> {key: CUDA tensor}: uint8 (N,H,W,3) for RGB,
+  uint8 (N,H,W) for 8-bit grey, 16-bit grey values as int16 (N,H,W) bit patterns (the convention of
+  datasets.indoor_datasets.RAW_DTYPES).  An item is an encoded PNG, or a PngPlane that parse_png
+  already made.  Geometry is equal within a key (ValueError otherwise).
+
+  Encoded items are parsed and inflated on a thread pool of `threads` workers (zlib releases the
+  GIL); `threads` is capped at 16.  The descriptor table and all filtered streams go into one pinned
+  host buffer, one asynchronous copy on the current stream takes it to the device, and one launch
+  reconstructs every plane of every key.  A non-CUDA device raises Se3dsHipError."""
+  dev = torch.device(device)
+  if dev.type != 'cuda':
+    raise _lib.Se3dsHipError('decode_png_batch reconstructs on an MI355X (cuda) device; got '
+                             f'{dev}.  There is no CPU fallback.')
+  if dev.index is None:
+    dev = torch.device('cuda', torch.cuda.current_device())
+  if not bufs_by_key or any(len(v) == 0 for v in bufs_by_key.values()):
+    raise ValueError('decode_png_batch: nothing to decode')
+  threads = max(1, min(int(threads), MAX_THREADS))
+  keys = list(bufs_by_key)
+  flat = [item for k in keys for item in bufs_by_key[k]]
+  if all(isinstance(item, PngPlane) for item in flat):
+    planes = flat
+  else:
+    with concurrent.futures.ThreadPoolExecutor(max_workers=threads) as pool:
+      planes = list(pool.map(_as_plane, flat))
+
+  L = _lib.lib()
+  fields = L.se3ds_png_unfilter_fields()
+  table = np.zeros((len(planes), fields), np.int64)
+  offset = (table.nbytes + 15) & ~15     # the streams follow the table, 16-byte aligned
+  out, idx = {}, 0
+  for k in keys:
+    group = planes[idx:idx + len(bufs_by_key[k])]
+    p0 = group[0]
+    for p in group:
+      if p[:4] != p0[:4]:
+        raise ValueError(f'{k}: a {p.height}x{p.width} PNG of {p.channels} channels at bit depth '
+                         f'{p.bit_depth} in a batch of {p0.height}x{p0.width}, {p0.channels}, '
+                         f'{p0.bit_depth}')
+    shape = (len(group), p0.height, p0.width) + ((3,) if p0.channels == 3 else ())
+    out[k] = torch.empty(shape, dtype=torch.int16 if p0.bit_depth == 16 else torch.uint8, device=dev)
+    plane_bytes = p0.height * p0.row_bytes
+    for i, p in enumerate(group):
+      table[idx + i] = (offset, out[k].data_ptr() + i * plane_bytes, p.height, p.row_bytes,
+                        p.bytes_per_pixel, int(p.bit_depth == 16))
+      offset += (len(p.filtered) + 15) & ~15
+    idx += len(group)
+
+  with torch.cuda.device(dev):
+    staging = torch.empty((offset,), dtype=torch.uint8, pin_memory=True)
+    host = staging.numpy()
+    host[:table.nbytes] = table.reshape(-1).view(np.uint8)
+    for row, p in zip(table, planes):
+      host[row[0]:row[0] + len(p.filtered)] = np.frombuffer(p.filtered, np.uint8)
+    # one copy: the device buffer starts with the table, and the table's offsets count from its base.
+    # Copy and kernel are queued on the current stream; the caching allocators (pinned and device)
+    # hand a freed block out again only behind that work.
+    device_buf = staging.to(dev, non_blocking=True)
+    rc = L.se3ds_png_unfilter(_lib.ptr(device_buf), offset, _lib.ptr(device_buf), table.ctypes.data,
+                              len(planes), _lib.stream())
+    _lib.check(rc, 'se3ds_png_unfilter')
+  return out
