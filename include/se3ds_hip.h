@@ -679,7 +679,8 @@ int se3ds_video_transform(const float* image, const uint8_t* segmentation,
                           uint8_t* o_pd_seg, float* o_depth, float* o_pd_depth, void* stream);
 
 /* PNG reconstruction (un-filtering) of a whole batch in one launch -- the second half of
- * tf.image.decode_png (datasets/indoor_datasets.py:185-228); the host inflates.  csrc/png.hip.
+ * tf.image.decode_png (datasets/indoor_datasets.py:185-228); the host or se3ds_png_inflate
+ * inflates.  csrc/png.hip.
  * src: the inflated streams of all images, one device buffer of src_bytes bytes; a stream is
  * height x (1 filter-type byte + row_bytes filtered bytes).  table: device int64
  * [n][se3ds_png_unfilter_fields() = 6] = source byte offset into src, destination device pointer
@@ -696,6 +697,35 @@ int se3ds_png_unfilter(const uint8_t* src, int64_t src_bytes, const int64_t* tab
                        const int64_t* host_table, int n, void* stream);
 int se3ds_png_unfilter_fields(void);
 int se3ds_png_unfilter_max_row_bytes(void);
+
+/* zlib inflate (RFC 1950 / 1951) of the IDAT streams of a whole batch in one launch, in front of
+ * se3ds_png_unfilter on the same stream -- the first half of tf.image.decode_png, for callers that
+ * do not inflate on the host.  csrc/inflate.hip, decoder in csrc/inflate_core.h.
+ * buf: one device buffer of buf_bytes bytes, 8-byte aligned, that BEGINS with the device copy of
+ * the table and holds the compressed streams behind it.  table: int64
+ * [n][se3ds_png_inflate_fields() = 5] = byte offset of the compressed stream in buf (not inside the
+ * table), its length, byte offset of the stream's region in workspace, expected inflated length
+ * (height x pitch), scan-line pitch (1 filter-type byte + row_bytes).  workspace: device buffer of
+ * workspace_bytes bytes; a stream's region receives the inflated, still filtered scan lines, laid
+ * out as se3ds_png_unfilter reads them (regions 16-byte aligned are written 16 bytes per lane, others
+ * bytewise; regions must not overlap).  One wavefront per stream; the 32 KiB window is an LDS ring
+ * of se3ds_png_inflate_ring_bytes() bytes.
+ * status_dev: device int32 [n], written by the launch: 0 = the stream inflated to exactly the
+ * expected length, its Adler-32 matched and every scan line starts with a filter type <= 4;
+ * otherwise the code of `enum class Status` (csrc/inflate_core.h) in the low 8 bits -- for
+ * BAD_FILTER with the filter-type byte in bits 8-15 and its row (saturating at 32767) in bits
+ * 16-30 -- and the region is zero from the end of the last 16 KiB granule written before the
+ * failure (for a failure in the trailer: from the last inflated byte) on.  The kernel reads the compressed bytes only inside [offset, offset + length) and writes only inside
+ * the region, whatever the stream says.
+ * host_table: the HOST copy of the table, validated here before anything runs (BADSHAPE: n < 1 or
+ * > 65535, a null or misaligned pointer, a range that leaves its buffer or enters the table, a
+ * length above 2^31 - 1, a pitch < 2, an expected length that is no multiple of the pitch).
+ * Deterministic. */
+int se3ds_png_inflate(const uint8_t* buf, int64_t buf_bytes, uint8_t* workspace,
+                      int64_t workspace_bytes, const int64_t* host_table, int n,
+                      int32_t* status_dev, void* stream);
+int se3ds_png_inflate_fields(void);
+int se3ds_png_inflate_ring_bytes(void);
 
 /* ======================================================================================
  * VLN perturbation augmentation -- inference/perturbation_utils.py:63-70.  csrc/perturb.hip.

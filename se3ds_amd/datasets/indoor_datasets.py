@@ -5,7 +5,8 @@ caller (uint8 / uint16 frames, what `tf.image.decode_png` yields, :185-228, as C
 straight from the published TFRecord files: `R2RImageDataset._parse` (:125-247) reads a record with
 utils/tf_records.py, `input_fn` (datasets/base_dataset.py:105-150) lists, repeats, shuffles and
 batches them, and utils/png.py decodes the seven PNGs of every example -- inflate on a small host
-thread pool, reconstruction of the whole batch in one launch (`se3ds_png_unfilter`).  TensorFlow is
+thread pool (or, with inflate='device', in one launch of `se3ds_png_inflate`), reconstruction of the
+whole batch in one launch (`se3ds_png_unfilter`).  TensorFlow is
 not needed.  Not built: sharding over several input pipelines beyond the seed offset, `cache`, the
 RE10K records (`visible_mask`, `_transform_fn_re10k`).
 
@@ -188,11 +189,12 @@ class R2RImageDataset:
         'bbox': FixedLenFeature([4], 'float32', [0.0, 0.0, 0.0, 0.0]),
     }
 
-  def _parse(self, record: bytes) -> dict:
+  def _parse(self, record: bytes, inflate: str = 'host') -> dict:
     """One serialized tf.train.Example -> the host half of the reference's `_parse` (:125-247): the
     seven planes of RAW_DTYPES as `png.PngPlane`s (container parsed, IDAT inflated, NOT yet
     reconstructed -- `png.decode_png_batch` does that for a whole batch on the device), plus
-    dataset_type, depth_scale, bbox and, with return_filename, filename and scan_id.
+    dataset_type, depth_scale, bbox and, with return_filename, filename and scan_id.  With
+    inflate='device' the planes are `png.PngStream`s: the container is walked, nothing is inflated.
 
     A plane that is not (preprocessed_image_height, 2 * preprocessed_image_height) raises
     ValueError, as `set_shape` does; so does one of another kind than the reference decodes it to
@@ -207,7 +209,7 @@ class R2RImageDataset:
     out = dict(dataset_type=np.int64(ex['dataset_type']))
     for name, (feature, channels, depth) in IMAGE_PLANES.items():
       try:
-        plane = png.parse_png(ex[feature])
+        plane = (png.parse_png if inflate == 'host' else png.parse_png_container)(ex[feature])
       except (ValueError, NotImplementedError) as e:
         raise type(e)(f'{feature}: {e}') from None
       if (plane.height, plane.width) != (h, w):
@@ -268,7 +270,7 @@ class R2RImageDataset:
                num_epochs: Optional[int] = None, shuffle: bool = False,
                shuffle_buffer_size: int = 1000, file_pattern: Optional[str] = None, seed: int = 1,
                input_pipeline_id: int = 0, device=None, decode_threads: int = 4,
-               verify_crc: bool = False) -> Iterator[Dict[str, torch.Tensor]]:
+               verify_crc: bool = False, inflate: str = 'host') -> Iterator[Dict[str, torch.Tensor]]:
     """Generator of step batches on the device, from TFRecord files: the dict `device_transform`
     returns plus `depth_scale` fp32 (N,) (and, with return_filename, the host lists `filename` and
     `scan_id`).  This is what GANManager.train(train_ds=...) takes.
@@ -286,9 +288,17 @@ class R2RImageDataset:
     range -- a few hundred ms per record on the generator's own thread, where no prefetch hides it
     and the inflate workers stall behind it.  Damage still surfaces: every PNG chunk carries a
     CRC-32 that parse_png checks with zlib (C code), a broken protobuf or a wrong geometry raises,
-    and a lost record boundary ends in `truncated record`.  Switch it on to audit a file once."""
+    and a lost record boundary ends in `truncated record`.  Switch it on to audit a file once.
+
+    inflate='device': the workers walk the PNG containers only and the IDAT streams are inflated on
+    the device (`png.decode_png_batch_async`).  The upload, inflate, reconstruction and transform of
+    the NEXT batch are queued on the current stream before the current batch is yielded, and a
+    batch's status words are waited for just before it is yielded -- the overlap the host path gets
+    from its pool.  A stream that does not inflate raises ValueError naming plane, index and
+    reason.  The batches are the same bit for bit."""
     if batch_size <= 0:
       raise ValueError(f'batch_size {batch_size}')
+    png.check_inflate_mode(inflate)
     dev = torch.device(device if device is not None else f'cuda:{torch.cuda.current_device()}')
     if dev.type != 'cuda':
       raise _lib.Se3dsHipError(f'input_fn decodes and transforms on an MI355X (cuda) device; got {dev}.'
@@ -304,25 +314,51 @@ class R2RImageDataset:
     def submit(pool):
       futures = []
       for rec in records:
-        futures.append(pool.submit(self._parse, rec))
+        futures.append(pool.submit(self._parse, rec, inflate))
         if len(futures) == batch_size:
           return futures
       return None   # the remainder is dropped
 
+    def finish(examples, raw):
+      params = [self.draw_params(draw_rng, h0, w0) for _ in examples]
+      batch = self.device_transform(raw, params)
+      batch['depth_scale'] = torch.from_numpy(
+          np.array([e['depth_scale'] for e in examples], F32)).to(dev)
+      if self.return_filename:
+        batch['filename'] = [e['filename'] for e in examples]
+        batch['scan_id'] = [e['scan_id'] for e in examples]
+      return batch
+
+    def enqueue(futures):
+      """A batch queued on the device with its inflate unchecked, or the exception that stopped it
+      (raised when the batch's turn comes, as on the host path)."""
+      if futures is None:
+        return None
+      try:
+        examples = [f.result() for f in futures]
+        raw, check = png.decode_png_batch_async({k: [e[k] for e in examples] for k in RAW_DTYPES}, dev)
+        return finish(examples, raw), check
+      except Exception as e:   # noqa: BLE001  re-raised below
+        return e
+
     with concurrent.futures.ThreadPoolExecutor(max_workers=threads) as pool:
       pending = submit(pool)
+      if inflate == 'device':
+        queued = enqueue(pending)
+        while queued is not None:
+          if isinstance(queued, Exception):
+            raise queued
+          following = enqueue(submit(pool))   # queued behind this batch, ahead of the caller's step
+          batch, check = queued
+          check.check()
+          yield batch
+          queued = following
+        return
       while pending is not None:
         examples = [f.result() for f in pending]
         pending = submit(pool)   # inflates under the step that consumes the batch below
         raw = png.decode_png_batch({k: [e[k] for e in examples] for k in RAW_DTYPES}, dev, threads)
-        params = [self.draw_params(draw_rng, h0, w0) for _ in examples]
-        batch = self.device_transform(raw, params)
-        batch['depth_scale'] = torch.from_numpy(
-            np.array([e['depth_scale'] for e in examples], F32)).to(dev)
-        if self.return_filename:
-          batch['filename'] = [e['filename'] for e in examples]
-          batch['scan_id'] = [e['scan_id'] for e in examples]
-        yield batch
+        yield finish(examples, raw)
 
 
 VIDEO_PLANES = dict(segmentation=torch.uint8, pathdreamer_segmentation=torch.uint8,
@@ -560,11 +596,16 @@ class R2RVideoDataset:
       epoch += 1
 
   def input_fn(self, examples, batch_size: int, seed: int = 0, num_epochs: Optional[int] = None,
-               device=None) -> Iterator[Dict[str, torch.Tensor]]:
+               device=None, inflate: str = 'host') -> Iterator[Dict[str, torch.Tensor]]:
     """Generator of transformed batches on the device: per batch stack, upload, draw, transform.
     This is the object handed to EvalMetric(ds=...), which draws eval_num // batch_size + 1
     batches per pass and makes several passes, so the default stream never ends.  String-valued
-    entries (scan_id with return_filename) stay on the host."""
+    entries (scan_id with return_filename) stay on the host.
+
+    `inflate` ('host' or 'device') is R2RImageDataset.input_fn's argument, accepted so that one
+    configuration serves both datasets; the trajectory records carry serialized tensors, not PNGs,
+    so there is nothing to inflate and both values give the same batches."""
+    png.check_inflate_mode(inflate)
     dev = torch.device(device if device is not None else f'cuda:{torch.cuda.current_device()}')
     rng = np.random.default_rng(seed)
     for batch in self.batch_examples(examples, batch_size, num_epochs):

@@ -1,13 +1,17 @@
-"""PNG decoding without an imaging package: the container and the inflate on the host, the
-reconstruction (un-filtering) of every plane of a batch on the device in one launch
-(`se3ds_png_unfilter`, csrc/png.hip).  This is tf.image.decode_png as the reference's
-`R2RImageDataset._parse` uses it (datasets/indoor_datasets.py:185-228): 8-bit RGB, 8-bit grey and
-16-bit grey, non-interlaced.  Written from the PNG specification (ISO/IEC 15948, sections 5, 9, 11).
-There is no CPU fallback for the reconstruction."""
+"""PNG decoding without an imaging package: the container on the host, the reconstruction
+(un-filtering) of every plane of a batch on the device in one launch (`se3ds_png_unfilter`,
+csrc/png.hip), and the zlib inflate between them either on the host (the default: `zlib` on a small
+thread pool) or, with inflate='device', on the device as well (`se3ds_png_inflate`,
+csrc/inflate.hip, one wavefront per plane in front of the reconstruction).  This is
+tf.image.decode_png as the reference's `R2RImageDataset._parse` uses it
+(datasets/indoor_datasets.py:185-228): 8-bit RGB, 8-bit grey and 16-bit grey, non-interlaced.
+Written from the PNG specification (ISO/IEC 15948, sections 5, 9, 11).  There is no CPU fallback for
+the reconstruction, and none for the device inflate."""
 import concurrent.futures
+import enum
 import struct
 import zlib
-from typing import Dict, NamedTuple, Sequence, Union
+from typing import Dict, List, NamedTuple, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -39,11 +43,27 @@ class PngPlane(NamedTuple):
     return self.width * self.bytes_per_pixel
 
 
-def parse_png(buf: bytes) -> PngPlane:
-  """Signature, chunk walk with CRC check, IHDR, the concatenated IDAT chunks inflated.  Supported:
-  colour type 0 at bit depth 8 or 16 and colour type 2 at bit depth 8, non-interlaced; any other
-  legal kind raises NotImplementedError naming it, every malformed input ValueError -- including a
-  filter-type byte above 4, so that the kernel never sees one."""
+class PngStream(NamedTuple):
+  """A parsed, NOT inflated PNG: `compressed` is the zlib stream of the joined IDAT chunks, which
+  inflates to height scan lines of one filter-type byte + row_bytes filtered bytes."""
+  height: int
+  width: int
+  bit_depth: int
+  channels: int
+  compressed: bytes
+
+  @property
+  def bytes_per_pixel(self):
+    return self.channels * self.bit_depth // 8
+
+  @property
+  def row_bytes(self):
+    return self.width * self.bytes_per_pixel
+
+
+def _walk(buf: bytes) -> Tuple[int, int, int, int, bytes]:
+  """The container half of parse_png and parse_png_container: signature, chunk walk with CRC check,
+  IHDR and kind checks -> height, width, bit depth, channels, the joined IDAT chunks."""
   buf = bytes(buf)
   if buf[:8] != SIGNATURE:
     raise ValueError('not a PNG: bad signature')
@@ -94,10 +114,25 @@ def parse_png(buf: bytes) -> PngPlane:
     raise NotImplementedError(f'PNG kind not supported: {kind}')
   if not idat:
     raise ValueError('PNG: no IDAT chunk')
-  channels = 3 if colour == 2 else 1
+  return height, width, depth, 3 if colour == 2 else 1, b''.join(idat)
+
+
+def parse_png_container(buf: bytes) -> PngStream:
+  """parse_png without the inflate: the same chunk walk, CRC and kind checks with the same
+  messages.  What the stream inflates to is checked where it is inflated: on the device, by
+  decode_png_batch(..., inflate='device')."""
+  return PngStream(*_walk(buf))
+
+
+def parse_png(buf: bytes) -> PngPlane:
+  """Signature, chunk walk with CRC check, IHDR, the concatenated IDAT chunks inflated.  Supported:
+  colour type 0 at bit depth 8 or 16 and colour type 2 at bit depth 8, non-interlaced; any other
+  legal kind raises NotImplementedError naming it, every malformed input ValueError -- including a
+  filter-type byte above 4, so that the kernel never sees one."""
+  height, width, depth, channels, compressed = _walk(buf)
   row_bytes = width * channels * depth // 8
   try:
-    filtered = zlib.decompress(b''.join(idat))
+    filtered = zlib.decompress(compressed)
   except zlib.error as e:
     raise ValueError(f'PNG: the IDAT stream does not inflate: {e}') from None
   if len(filtered) != height * (1 + row_bytes):
@@ -112,17 +147,26 @@ def _as_plane(item: Union[bytes, PngPlane]) -> PngPlane:
   return item if isinstance(item, PngPlane) else parse_png(item)
 
 
-def decode_png_batch(bufs_by_key: Dict[str, Sequence[Union[bytes, PngPlane]]], device,
-                     threads: int = 4) -> Dict[str, torch.Tensor]:
+def decode_png_batch(bufs_by_key: Dict[str, Sequence[Union[bytes, PngPlane, PngStream]]], device,
+                     threads: int = 4, inflate: str = 'host') -> Dict[str, torch.Tensor]:
   """{key: the N PNGs of one plane of a batch} -> {key: CUDA tensor}: uint8 (N,H,W,3) for RGB,
   uint8 (N,H,W) for 8-bit grey, 16-bit grey values as int16 (N,H,W) bit patterns (the convention of
   datasets.indoor_datasets.RAW_DTYPES).  An item is an encoded PNG, or a PngPlane that parse_png
   already made.  Geometry is equal within a key (ValueError otherwise).
 
+  inflate='device': the IDAT streams are inflated on the device too -- decode_png_batch_async
+  followed by its wait; an item is then an encoded PNG or a PngStream, and a stream that does not
+  inflate raises ValueError naming key, index within the key and reason.  The rest of this text is
+  the default, inflate='host'.
+
   Encoded items are parsed and inflated on a thread pool of `threads` workers (zlib releases the
   GIL); `threads` is capped at 16.  The descriptor table and all filtered streams go into one pinned
   host buffer, one asynchronous copy on the current stream takes it to the device, and one launch
   reconstructs every plane of every key.  A non-CUDA device raises Se3dsHipError."""
+  if check_inflate_mode(inflate) == 'device':
+    out, pending = decode_png_batch_async(bufs_by_key, device)
+    pending.check()
+    return out
   dev = torch.device(device)
   if dev.type != 'cuda':
     raise _lib.Se3dsHipError('decode_png_batch reconstructs on an MI355X (cuda) device; got '
@@ -176,3 +220,157 @@ def decode_png_batch(bufs_by_key: Dict[str, Sequence[Union[bytes, PngPlane]]], d
                               len(planes), _lib.stream())
     _lib.check(rc, 'se3ds_png_unfilter')
   return out
+
+
+# ------------------------------------------------------------------------------ device inflate
+class InflateStatus(enum.IntEnum):
+  """The status word's low byte (csrc/inflate_core.h, enum class Status: the same names)."""
+  OK = 0
+  TRUNCATED = 1
+  BAD_HEADER = 2
+  BAD_BLOCK_TYPE = 3
+  BAD_STORED_LENGTH = 4
+  BAD_COUNTS = 5
+  OVER_SUBSCRIBED = 6
+  INCOMPLETE = 7
+  BAD_REPEAT = 8
+  NO_END_OF_BLOCK = 9
+  BAD_CODE = 10
+  BAD_DISTANCE = 11
+  TOO_LONG = 12
+  TOO_SHORT = 13
+  BAD_ADLER = 14
+  BAD_FILTER = 15
+
+
+_INFLATE_REASONS = {
+    InflateStatus.TRUNCATED: 'incomplete or truncated stream',
+    InflateStatus.BAD_HEADER: 'incorrect zlib header',
+    InflateStatus.BAD_BLOCK_TYPE: 'invalid block type',
+    InflateStatus.BAD_STORED_LENGTH: 'invalid stored block lengths',
+    InflateStatus.BAD_COUNTS: 'too many length or distance symbols',
+    InflateStatus.OVER_SUBSCRIBED: 'over-subscribed set of code lengths',
+    InflateStatus.INCOMPLETE: 'incomplete set of code lengths',
+    InflateStatus.BAD_REPEAT: 'invalid bit length repeat',
+    InflateStatus.NO_END_OF_BLOCK: 'missing end-of-block code',
+    InflateStatus.BAD_CODE: 'invalid literal/length or distance code',
+    InflateStatus.BAD_DISTANCE: 'distance beyond the start of the output',
+    InflateStatus.BAD_ADLER: 'incorrect data check',
+}
+
+
+def check_inflate_mode(inflate: str) -> str:
+  if inflate not in ('host', 'device'):
+    raise ValueError(f"inflate: 'host' or 'device', got {inflate!r}")
+  return inflate
+
+
+def inflate_failure(word: int, stream: PngStream) -> str:
+  """The message of a non-zero status word of se3ds_png_inflate for `stream`."""
+  code = InflateStatus(word & 0xff)
+  if code in _INFLATE_REASONS:
+    return f'the IDAT stream does not inflate: {_INFLATE_REASONS[code]}'
+  if code == InflateStatus.BAD_FILTER:
+    return f'filter type {(word >> 8) & 0xff} in row {word >> 16}'
+  more = 'more' if code == InflateStatus.TOO_LONG else 'fewer'
+  return f'{more} inflated bytes than {stream.height} x (1 + {stream.row_bytes})'
+
+
+class PendingDecode:
+  """The device inflate of one batch in flight: `check()` waits for the status words and raises
+  ValueError for the first plane that failed.  The output tensors are valid (and may be read on the
+  stream the batch was launched on) only if check() returns."""
+
+  def __init__(self, event, status, names: List[Tuple[str, int]], streams: List[PngStream]):
+    self._event, self._status, self._names, self._streams = event, status, names, streams
+
+  def check(self) -> None:
+    self._event.synchronize()
+    words = self._status.numpy()
+    bad = np.flatnonzero(words)
+    if bad.size:
+      i = int(bad[0])
+      key, index = self._names[i]
+      raise ValueError(f'{key}[{index}]: {inflate_failure(int(words[i]), self._streams[i])}')
+
+
+def _as_stream(item: Union[bytes, PngStream]) -> PngStream:
+  if isinstance(item, PngStream):
+    return item
+  if isinstance(item, PngPlane):
+    raise ValueError("a PngPlane is already inflated: decode it with inflate='host'")
+  return parse_png_container(item)
+
+
+def decode_png_batch_async(bufs_by_key: Dict[str, Sequence[Union[bytes, PngStream]]], device
+                           ) -> Tuple[Dict[str, torch.Tensor], PendingDecode]:
+  """decode_png_batch with the inflate on the device, without the wait: -> (out, pending).  An item
+  is an encoded PNG or a PngStream of parse_png_container.  Both descriptor tables and all
+  compressed streams go into one pinned host buffer and one asynchronous copy; then, on the current
+  stream, `se3ds_png_inflate` (one wavefront per plane) writes the filtered scan lines into a device
+  workspace, `se3ds_png_unfilter` reconstructs from it, and the status words are copied back with an
+  event behind them.  `pending.check()` waits on that event and raises ValueError naming key, index
+  within the key and reason for the first plane whose stream did not inflate to its geometry; `out`
+  counts only once it has returned.  A non-CUDA device raises Se3dsHipError."""
+  dev = torch.device(device)
+  if dev.type != 'cuda':
+    raise _lib.Se3dsHipError('decode_png_batch inflates and reconstructs on an MI355X (cuda) device; '
+                             f'got {dev}.  There is no CPU fallback.')
+  if dev.index is None:
+    dev = torch.device('cuda', torch.cuda.current_device())
+  if not bufs_by_key or any(len(v) == 0 for v in bufs_by_key.values()):
+    raise ValueError('decode_png_batch: nothing to decode')
+  keys = list(bufs_by_key)
+  streams = [_as_stream(item) for k in keys for item in bufs_by_key[k]]
+  names = [(k, i) for k in keys for i in range(len(bufs_by_key[k]))]
+
+  L = _lib.lib()
+  n = len(streams)
+  inflate_table = np.zeros((n, L.se3ds_png_inflate_fields()), np.int64)
+  unfilter_table = np.zeros((n, L.se3ds_png_unfilter_fields()), np.int64)
+  unfilter_at = inflate_table.nbytes               # the device buffer starts with the inflate table,
+  offset = (unfilter_at + unfilter_table.nbytes + 15) & ~15   # then the other, then the streams
+  out, idx, workspace_bytes = {}, 0, 0
+  for k in keys:
+    group = streams[idx:idx + len(bufs_by_key[k])]
+    p0 = group[0]
+    for p in group:
+      if p[:4] != p0[:4]:
+        raise ValueError(f'{k}: a {p.height}x{p.width} PNG of {p.channels} channels at bit depth '
+                         f'{p.bit_depth} in a batch of {p0.height}x{p0.width}, {p0.channels}, '
+                         f'{p0.bit_depth}')
+    shape = (len(group), p0.height, p0.width) + ((3,) if p0.channels == 3 else ())
+    out[k] = torch.empty(shape, dtype=torch.int16 if p0.bit_depth == 16 else torch.uint8, device=dev)
+    plane_bytes = p0.height * p0.row_bytes
+    inflated = p0.height * (1 + p0.row_bytes)
+    for i, p in enumerate(group):
+      inflate_table[idx + i] = (offset, len(p.compressed), workspace_bytes, inflated, 1 + p.row_bytes)
+      unfilter_table[idx + i] = (workspace_bytes, out[k].data_ptr() + i * plane_bytes, p.height,
+                                 p.row_bytes, p.bytes_per_pixel, int(p.bit_depth == 16))
+      offset += (len(p.compressed) + 15) & ~15
+      workspace_bytes += (inflated + 15) & ~15     # 16-byte aligned: the flush stores 16 bytes a lane
+    idx += len(group)
+
+  with torch.cuda.device(dev):
+    staging = torch.empty((offset,), dtype=torch.uint8, pin_memory=True)
+    host = staging.numpy()
+    host[:unfilter_at] = inflate_table.reshape(-1).view(np.uint8)
+    host[unfilter_at:unfilter_at + unfilter_table.nbytes] = unfilter_table.reshape(-1).view(np.uint8)
+    for row, p in zip(inflate_table, streams):
+      host[row[0]:row[0] + row[1]] = np.frombuffer(p.compressed, np.uint8)
+    # as in the host path: copies and kernels are queued on the current stream, and the caching
+    # allocators (pinned and device) hand a freed block out again only behind that work
+    device_buf = staging.to(dev, non_blocking=True)
+    workspace = torch.empty((workspace_bytes,), dtype=torch.uint8, device=dev)
+    status = torch.empty((n,), dtype=torch.int32, device=dev)
+    rc = L.se3ds_png_inflate(_lib.ptr(device_buf), offset, _lib.ptr(workspace), workspace_bytes,
+                             inflate_table.ctypes.data, n, _lib.ptr(status), _lib.stream())
+    _lib.check(rc, 'se3ds_png_inflate')
+    rc = L.se3ds_png_unfilter(_lib.ptr(workspace), workspace_bytes, _lib.ptr(device_buf) + unfilter_at,
+                              unfilter_table.ctypes.data, n, _lib.stream())
+    _lib.check(rc, 'se3ds_png_unfilter')
+    status_host = torch.empty((n,), dtype=torch.int32, pin_memory=True)
+    status_host.copy_(status, non_blocking=True)
+    event = torch.cuda.Event()
+    event.record()
+  return out, PendingDecode(event, status_host, names, streams)

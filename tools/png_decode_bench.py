@@ -14,7 +14,15 @@ Reported, each named for what it is:
             around a device synchronise)
 The decoded planes are compared with the synthesised pixels before anything is timed.
 
-  python tools/png_decode_bench.py [--iters 50] [--rounds 3] [--out FILE.json]
+--inflate device | both adds the same batch with the inflate on the device (`se3ds_png_inflate`):
+  device_inflate_kernel_ms   the inflate launch over the 56 compressed streams already resident
+  device_unfilter_kernel_ms  the reconstruction behind it, from the inflate's workspace
+  device_upload_mib / _ms    the one pinned copy of both tables + the COMPRESSED streams
+  decode_png_batch_device_ms the whole decode_png_batch(inflate='device') call from PngStreams
+--inflate host (the default) reports what the tool always did; `both` is the comparison DESIGN.md
+section 3.8 asks for: device_inflate_kernel_ms against inflate_pool[4].batch_ms on one machine.
+
+  python tools/png_decode_bench.py [--inflate host|device|both] [--iters 50] [--rounds 3] [--out FILE.json]
 """
 import argparse
 import concurrent.futures
@@ -111,6 +119,7 @@ def main():
   ap.add_argument('--iters', type=int, default=50)
   ap.add_argument('--rounds', type=int, default=3)
   ap.add_argument('--out', default=None)
+  ap.add_argument('--inflate', choices=('host', 'device', 'both'), default='host')
   a = ap.parse_args()
   if not torch.cuda.is_available():
     raise SystemExit('png_decode_bench needs an MI355X: a CPU run cannot give a time')
@@ -138,7 +147,79 @@ def main():
     if not (g == want).all():
       raise SystemExit(f'{k}: decoded planes differ from the synthesised pixels')
   res['equal_to_source'] = True
+  res['inflate'] = a.inflate
+  if a.inflate in ('device', 'both'):
+    device_inflate(a, res, dev, keys, encoded, got)
+  if a.inflate in ('host', 'both'):
+    host_inflate(a, res, dev, keys, encoded, pixels)
+  line = json.dumps(res)
+  print(line)
+  if a.out:
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, 'w') as f:
+      f.write(line + '\n')
 
+
+def device_inflate(a, res, dev, keys, encoded, want):
+  """The batch with the inflate on the device; `want`: the host path's decode of the same PNGs."""
+  got = png.decode_png_batch(encoded, dev, inflate='device')
+  for k in keys:
+    if not torch.equal(got[k], want[k]):
+      raise SystemExit(f"{k}: inflate='device' differs from inflate='host'")
+  streams = [png.parse_png_container(b) for k in keys for b in encoded[k]]
+  L = _lib.lib()
+  n = len(streams)
+  itab = np.zeros((n, L.se3ds_png_inflate_fields()), np.int64)
+  utab = np.zeros((n, L.se3ds_png_unfilter_fields()), np.int64)
+  offset = (itab.nbytes + utab.nbytes + 15) & ~15
+  ws, outs = 0, []
+  for i, p in enumerate(streams):
+    inflated = p.height * (1 + p.row_bytes)
+    outs.append(torch.empty(p.height * p.row_bytes, dtype=torch.uint8, device=dev))
+    itab[i] = (offset, len(p.compressed), ws, inflated, 1 + p.row_bytes)
+    utab[i] = (ws, outs[-1].data_ptr(), p.height, p.row_bytes, p.bytes_per_pixel, int(p.bit_depth == 16))
+    offset += (len(p.compressed) + 15) & ~15
+    ws += (inflated + 15) & ~15
+  staging = torch.empty((offset,), dtype=torch.uint8, pin_memory=True)
+  host = staging.numpy()
+  host[:itab.nbytes] = itab.reshape(-1).view(np.uint8)
+  host[itab.nbytes:itab.nbytes + utab.nbytes] = utab.reshape(-1).view(np.uint8)
+  for row, p in zip(itab, streams):
+    host[row[0]:row[0] + row[1]] = np.frombuffer(p.compressed, np.uint8)
+  dbuf = torch.empty((offset,), dtype=torch.uint8, device=dev)
+  workspace = torch.empty((ws,), dtype=torch.uint8, device=dev)
+  status = torch.empty((n,), dtype=torch.int32, device=dev)
+  upload = lambda: dbuf.copy_(staging, non_blocking=True)
+  inflate = lambda: _lib.check(L.se3ds_png_inflate(dbuf.data_ptr(), offset, workspace.data_ptr(), ws,
+                                                   itab.ctypes.data, n, status.data_ptr(), _lib.stream()),
+                               'se3ds_png_inflate')
+  unfilter = lambda: _lib.check(L.se3ds_png_unfilter(workspace.data_ptr(), ws, dbuf.data_ptr() + itab.nbytes,
+                                                     utab.ctypes.data, n, _lib.stream()),
+                                'se3ds_png_unfilter')
+  for _ in range(2):
+    upload()
+    inflate()
+    unfilter()
+  torch.cuda.synchronize()
+  if status.any():
+    raise SystemExit(f'device inflate status words: {status.tolist()}')
+  iters = max(1, a.iters // 5)   # the inflate is the long kernel of this tool
+  res['device_upload_mib'] = offset / 2 ** 20
+  res['device_upload_ms'] = [time_ms(upload, a.iters) for _ in range(a.rounds)]
+  res['device_inflate_kernel_ms'] = [time_ms(inflate, iters) for _ in range(a.rounds)]
+  res['device_unfilter_kernel_ms'] = [time_ms(unfilter, a.iters) for _ in range(a.rounds)]
+  by_key = {k: streams[i * BATCH:(i + 1) * BATCH] for i, k in enumerate(keys)}
+  whole = []
+  for _ in range(a.rounds):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(5):
+      png.decode_png_batch(by_key, dev, inflate='device')
+    whole.append((time.perf_counter() - t0) * 200)
+  res['decode_png_batch_device_ms'] = whole
+
+
+def host_inflate(a, res, dev, keys, encoded, pixels):
   # ---- inflate: one thread per plane kind, then the batch on pools
   per_plane = {}
   for k in keys:
@@ -206,12 +287,6 @@ def main():
     torch.cuda.synchronize()
     whole.append((time.perf_counter() - t0) * 100)
   res['decode_png_batch_from_planes_ms'] = whole
-  line = json.dumps(res)
-  print(line)
-  if a.out:
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, 'w') as f:
-      f.write(line + '\n')
 
 
 if __name__ == '__main__':
