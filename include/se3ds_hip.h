@@ -727,6 +727,30 @@ int se3ds_png_inflate(const uint8_t* buf, int64_t buf_bytes, uint8_t* workspace,
 int se3ds_png_inflate_fields(void);
 int se3ds_png_inflate_ring_bytes(void);
 
+/* CRC-32C (Castagnoli: reflected polynomial 0x82F63B78, init and final xor 0xffffffff; RFC 3720
+ * B.4, utils/tf_bundle.crc32c) of n byte ranges of one device buffer in one call -- the checksum of
+ * TFRecord frames and of the tensors of a checkpoint bundle.  csrc/crc32c.hip, arithmetic in
+ * csrc/crc32c_core.h.
+ * buf: device buffer of buf_bytes bytes, read only.  table_dev: device int64
+ * [n][se3ds_crc32c_fields() = 2] = byte offset into buf, length; offsets and lengths need no
+ * alignment and ranges may overlap.  crc_dev: device uint32 [n], receives the raw (unmasked) CRC of
+ * every range; length 0 gives 0.  workspace: device buffer of at least
+ * se3ds_crc32c_workspace_bytes(sum of the lengths, n) bytes, 8-byte aligned.
+ * The work of all ranges is cut into blocks of se3ds_crc32c_block_bytes() bytes, counted from the
+ * end of each range, and shared evenly among the wavefronts.  The kernels read buf only inside the
+ * ranges (also where they load 4 or 16 bytes at once) and write only crc_dev and the workspace.
+ * host_table: the HOST copy of the table, validated here before anything runs (BADSHAPE: n < 1, a
+ * null or misaligned pointer, a negative offset or length, a range that leaves [0, buf_bytes), a
+ * workspace that is too small); the kernels read only the device copy and skip a row of it that
+ * leaves the buffer.  Two launches on `stream`, no host synchronisation, integer arithmetic,
+ * deterministic. */
+int se3ds_crc32c_multi(const uint8_t* buf, int64_t buf_bytes, const int64_t* table_dev,
+                       const int64_t* host_table, int n, uint32_t* crc_dev, void* workspace,
+                       size_t workspace_bytes, void* stream);
+size_t se3ds_crc32c_workspace_bytes(int64_t total_bytes, int n);
+int se3ds_crc32c_fields(void);
+int se3ds_crc32c_block_bytes(void);
+
 /* ======================================================================================
  * VLN perturbation augmentation -- inference/perturbation_utils.py:63-70.  csrc/perturb.hip.
  * ====================================================================================== */

@@ -55,6 +55,10 @@ _SIGS = {
     'se3ds_png_inflate': (c_int, [c_p, c_i64, c_p, c_i64, c_p, c_int, c_p, c_p]),
     'se3ds_png_inflate_fields': (c_int, []),
     'se3ds_png_inflate_ring_bytes': (c_int, []),
+    'se3ds_crc32c_multi': (c_int, [c_p, c_i64, c_p, c_p, c_int, c_p, c_p, c_sz, c_p]),
+    'se3ds_crc32c_workspace_bytes': (c_sz, [c_i64, c_int]),
+    'se3ds_crc32c_fields': (c_int, []),
+    'se3ds_crc32c_block_bytes': (c_int, []),
     'se3ds_collision_count': (c_int, [c_p, c_int, c_int, c_int, c_p, c_p, c_p, c_f, c_int, c_p, c_p]),
     'se3ds_collision_check_windows': (c_int, [c_p, c_p, c_int, c_int, c_int, c_int]),
     'se3ds_perspective_to_pointcloud': (c_int, [c_p, c_p, c_int, c_int, c_int, c_p, c_p, c_int, c_f, c_p, c_p,

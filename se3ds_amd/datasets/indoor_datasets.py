@@ -236,7 +236,7 @@ class R2RImageDataset:
 
   def _records(self, files: List[str], num_epochs: Optional[int], shuffle: bool,
                shuffle_buffer_size: int, rng: np.random.Generator,
-               verify_crc: bool = False) -> Iterator[bytes]:
+               verify_crc=False) -> Iterator[bytes]:
     """files in order, records in file order, repeat, then tf.data's shuffle buffer: fill to
     `shuffle_buffer_size`, then emit a uniformly drawn slot and refill it; drain at the end."""
     def stream():
@@ -270,7 +270,7 @@ class R2RImageDataset:
                num_epochs: Optional[int] = None, shuffle: bool = False,
                shuffle_buffer_size: int = 1000, file_pattern: Optional[str] = None, seed: int = 1,
                input_pipeline_id: int = 0, device=None, decode_threads: int = 4,
-               verify_crc: bool = False, inflate: str = 'host') -> Iterator[Dict[str, torch.Tensor]]:
+               verify_crc=False, inflate: str = 'host') -> Iterator[Dict[str, torch.Tensor]]:
     """Generator of step batches on the device, from TFRecord files: the dict `device_transform`
     returns plus `depth_scale` fp32 (N,) (and, with return_filename, the host lists `filename` and
     `scan_id`).  This is what GANManager.train(train_ds=...) takes.
@@ -283,12 +283,15 @@ class R2RImageDataset:
     The records of the NEXT batch are parsed and inflated on `decode_threads` workers (capped at
     16) while the caller runs the current step; reconstruction is one launch per batch.
 
-    `verify_crc` is off by default: the record checksum is utils/tf_bundle.crc32c, a Python byte
-    loop of about 5 MB/s that holds the GIL, and a 512 x 1024 record of seven PNGs is in the MB
-    range -- a few hundred ms per record on the generator's own thread, where no prefetch hides it
-    and the inflate workers stall behind it.  Damage still surfaces: every PNG chunk carries a
-    CRC-32 that parse_png checks with zlib (C code), a broken protobuf or a wrong geometry raises,
-    and a lost record boundary ends in `truncated record`.  Switch it on to audit a file once.
+    `verify_crc` is off by default.  True checks both checksums of every record with
+    utils/tf_bundle.crc32c, a Python byte loop of about 5 MB/s that holds the GIL -- a few hundred
+    ms per 512 x 1024 record of seven PNGs on the generator's own thread, where no prefetch hides
+    it: for auditing a file once.  'device' checks them with the CRC-32C kernel (utils/crc32c.py,
+    `tf_records.read_records(verify='device')`): the records are uploaded in batches of 64 MiB and
+    checked with one call per batch, at memory speed; whether it becomes the default
+    is decided from measurements, not here.  With the default, damage still surfaces in part:
+    every PNG chunk carries a CRC-32 that parse_png checks with zlib (C code), a broken protobuf or
+    a wrong geometry raises, and a lost record boundary ends in `truncated record`.
 
     inflate='device': the workers walk the PNG containers only and the IDAT streams are inflated on
     the device (`png.decode_png_batch_async`).  The upload, inflate, reconstruction and transform of
@@ -451,16 +454,16 @@ class R2RVideoDataset:
     return out
 
   def examples_from_tfrecords(self, split: Optional[str] = None, file_pattern: Optional[str] = None,
-                              verify_crc: bool = False) -> Callable[[], Iterator[dict]]:
+                              verify_crc=False) -> Callable[[], Iterator[dict]]:
     """The parsed examples of a split's TFRecord files (sorted, records in file order) as a
     zero-argument callable that returns a fresh iterator -- what `input_fn(examples=...)` and
     GANManager.test(eval_examples=...) take; one example is in memory at a time.
 
-    `verify_crc` is off by default, as in R2RImageDataset.input_fn and for the same reason, only
-    more so: a 512 x 1024 trajectory is roughly 100 MB of fp32, tens of seconds of the Python
-    CRC-32C per record.  Unlike the PNG planes, `tensor_content` carries no checksum of its own, so
-    with the default only the framing, the protobuf structure, the dtypes and the shapes are checked;
-    pass verify_crc=True to audit a file once."""
+    `verify_crc` is off by default, as in R2RImageDataset.input_fn.  Unlike the PNG planes,
+    `tensor_content` carries no checksum of its own, so with the default only the framing, the
+    protobuf structure, the dtypes and the shapes are checked.  True audits a file with the Python
+    CRC-32C (a 512 x 1024 trajectory is roughly 100 MB of fp32: tens of seconds per record);
+    'device' checks every record with the CRC-32C kernel (utils/crc32c.py) at memory speed."""
     files = _record_files(self.get_file_patterns(split, file_pattern))
 
     def examples():

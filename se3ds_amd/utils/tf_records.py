@@ -18,6 +18,7 @@ Formats, as implemented:
               the numeric lists packed (one length-delimited field) or unpacked (one field per value)
   TensorProto {1: dtype, 2: TensorShapeProto{2: Dim{1: size}}, 4: tensor_content}
 """
+import os
 import struct
 from typing import Dict, Iterable, Iterator, List, Tuple, Union
 
@@ -36,9 +37,21 @@ _VALUE_FIELDS = {5: 'float_val', 6: 'double_val', 7: 'int_val', 8: 'string_val',
 
 
 # ------------------------------------------------------------------------------- records
-def read_records(path: str, verify: bool = True) -> Iterator[bytes]:
+def read_records(path: str, verify: Union[bool, str] = True,
+                 device_batch_bytes: int = 64 << 20) -> Iterator[bytes]:
   """The payloads of a TFRecord file, in file order.  A truncated file raises ValueError naming the
-  path and the offset of the record; with `verify`, so does a wrong length or payload CRC."""
+  path and the offset of the record; with `verify`, so does a wrong length or payload CRC.
+
+  verify='device': both checksums of every record are computed on the device (utils/crc32c.py)
+  instead of by the Python byte loop.  Records are read until `device_batch_bytes` are pending, the
+  batch is uploaded once and its 2 ranges per record -- the 8-byte length field and the payload --
+  are checked in one call; then the payloads are yielded.  Errors are those of the host path, text
+  and offset included, and every record in front of the bad one is yielded first."""
+  if isinstance(verify, str):
+    if verify != 'device':
+      raise ValueError(f"verify {verify!r}: True, False or 'device'")
+    yield from _read_records_device(path, int(device_batch_bytes))
+    return
   with open(path, 'rb') as f:
     offset = 0
     while True:
@@ -59,6 +72,68 @@ def read_records(path: str, verify: bool = True) -> Iterator[bytes]:
         raise ValueError(f'{path}: payload checksum mismatch at offset {offset}')
       yield payload
       offset += 12 + length + 4
+
+
+def _read_records_device(path: str, batch_bytes: int) -> Iterator[bytes]:
+  """read_records(verify='device').  A record whose length field is damaged cannot be told from a
+  sound one before its checksum is known, so the reader never trusts a length beyond the end of the
+  file: whatever ends the reading (end of file, a truncation, a length that does not fit) first
+  has the pending records checked in file order, and the first bad checksum wins, as it does on
+  the host, where it is met first."""
+  import torch
+  from se3ds_amd.utils import crc32c as crc32c_dev
+
+  pending = []   # (offset, 8 length bytes, stored length crc, payload or None, stored payload crc)
+
+  def flush():
+    if not pending:
+      return
+    parts, offs, lens, pos = [], [], [], 0
+    for _, head8, _, payload, _ in pending:
+      for piece in (head8,) if payload is None else (head8, payload):
+        parts.append(piece)
+        offs.append(pos)
+        lens.append(len(piece))
+        pos += len(piece)
+    slab = torch.frombuffer(bytearray(b''.join(parts)), dtype=torch.uint8).cuda()
+    crcs = iter(crc32c_dev.crc32c_device(slab, offs, lens).tolist())
+    batch = list(pending)
+    pending.clear()
+    for offset, _, want_len, payload, want_payload in batch:
+      if unmask_crc(want_len) != next(crcs):
+        raise ValueError(f'{path}: length checksum mismatch at offset {offset}')
+      if payload is None:   # the header of a record whose body could not be read
+        return
+      if unmask_crc(want_payload) != next(crcs):
+        raise ValueError(f'{path}: payload checksum mismatch at offset {offset}')
+      yield payload
+
+  with open(path, 'rb') as f:
+    size = os.fstat(f.fileno()).st_size
+    offset = pending_bytes = 0
+    while True:
+      head = f.read(12)
+      if not head:
+        yield from flush()
+        return
+      if len(head) < 12:
+        yield from flush()
+        raise ValueError(f'{path}: truncated record header at offset {offset}')
+      length, = struct.unpack_from('<Q', head, 0)
+      want_len, = struct.unpack_from('<I', head, 8)
+      left = size - (offset + 12)
+      body = f.read(min(length + 4, max(left, 0)))
+      if len(body) < length + 4:
+        pending.append((offset, head[:8], want_len, None, 0))
+        yield from flush()   # raises if the length itself is damaged
+        raise ValueError(f'{path}: truncated record at offset {offset} '
+                         f'({len(body)} of {length + 4} bytes)')
+      pending.append((offset, head[:8], want_len, body[:length], struct.unpack_from('<I', body, length)[0]))
+      pending_bytes += 8 + length
+      offset += 12 + length + 4
+      if pending_bytes >= batch_bytes:
+        yield from flush()
+        pending_bytes = 0
 
 
 def write_records(path: str, records: Iterable[bytes]):
