@@ -757,3 +757,525 @@ def head_bwd(dy, y, x, kind, dtype=np.float64):
     return dy * (dtype(1) - t * t) * dtype(0.5)
   x = np.asarray(x, dtype=dtype)
   return np.where((x >= 0) & (x <= 1), dy, dtype(0))
+
+
+# =============================================================================================
+# Norm, pooling and pad references (NumPy float64; se3ds_amd/csrc/norm.hip and the pooling / pad /
+# copy kernels of pointwise.hip), written from the formulas of include/se3ds_hip.h and the TF
+# semantics only.  Every stage of the norm takes the previous stage's results as ARGUMENTS, so
+# each gets lattice inputs of its own: activations and gradients small integers, row factors /
+# rstd / gamma / alpha signed powers of two, mean / beta / shift small integers, count a power of
+# two (a free parameter: it need not equal the row count).  Every product, FMA and sum of any
+# algebraic rearrangement of the documented formula is then exact in fp32 and each output has one
+# legal value: the float64 result rounded once to the storage type.
+
+def rne_np(a, bf16):
+  """float64 -> the stored value: one rounding to fp32, then (bf16) one to nearest-even bf16."""
+  a = f32(a)
+  if bf16:
+    a = torch.from_numpy(np.ascontiguousarray(a)).bfloat16().float().numpy()
+  return a
+
+
+def exact32(a, name):
+  """Asserts that a float64 intermediate is an fp32 value (no rounding happened) and returns it."""
+  a = np.asarray(a, dtype=np.float64)
+  assert np.array_equal(f32(a).astype(np.float64), a), f'{name}: rounds in fp32'
+  return a
+
+
+def assert_all_pow2(a, name):
+  m, _ = np.frexp(np.abs(np.asarray(a, dtype=np.float64)))
+  assert np.all(m == 0.5), f'{name}: not signed powers of two'
+
+
+def small_ints(shape, seed, lo, hi, zero_share=0.0):
+  """float64 integers in [lo, hi]; a share of them forced to 0 (post-ReLU zeros, ties)."""
+  r = rng(seed)
+  a = r.integers(lo, hi + 1, shape).astype(np.float64)
+  if zero_share:
+    a[r.random(shape) < zero_share] = 0.0
+  return a
+
+
+def signed_pow2(shape, seed, mags=(0.5, 1.0, 2.0), signed=True):
+  r = rng(seed)
+  a = np.asarray(mags, dtype=np.float64)[r.integers(0, len(mags), shape)]
+  return a * r.choice((-1.0, 1.0), shape) if signed else a
+
+
+def assert_exact_colsum(terms, name, quantum):
+  """Column sums over axis -2 that are exact in fp32 in ANY order: every term an integer multiple
+  of `quantum`, the sum of magnitudes of every column below 2^24 quanta.  Returns the sums."""
+  assert_pow2(quantum, name + ' quantum')
+  t = np.asarray(terms, dtype=np.float64) / quantum
+  assert np.array_equal(t, np.round(t)), f'{name}: terms off the lattice of {quantum}'
+  assert_reduction(float(np.abs(t).sum(axis=-2).max()) + 1, name)
+  return t.sum(axis=-2) * quantum
+
+
+def assert_any_order(quantum, bound, name):
+  """Every intermediate of any rearrangement is a multiple of `quantum` and at most `bound`."""
+  assert_pow2(quantum, name + ' quantum')
+  assert bound / quantum < LIMIT, f'{name}: {bound} / {quantum} >= 2^24'
+
+
+def _qmin(a, cap=1.0):
+  """Power-of-two quantum contributed by a factor whose values are signed powers of two."""
+  a = np.abs(np.asarray(a, dtype=np.float64))
+  return min(cap, float(a.min())) if a.size else cap
+
+
+def act_np(t, act, alpha):
+  if act == 1:
+    return np.where(t > 0, t, 0.0)
+  if act == 2:
+    assert_pow2(alpha, 'alpha')
+    return np.where(t > 0, t, t * alpha)
+  return t
+
+
+def act_grad_np(pos, act, alpha):
+  """Derivative of the activation from `pos` = (its stored output > 0)."""
+  if act == 1:
+    return np.where(pos, 1.0, 0.0)
+  if act == 2:
+    assert_pow2(alpha, 'alpha')
+    return np.where(pos, 1.0, float(alpha))
+  return np.ones(np.shape(pos))
+
+
+def pack_mask(y):
+  """act_mask: bit e of byte i = (y[8 i + e] > 0) over the flattened stored output."""
+  return np.packbits((np.asarray(y) > 0).reshape(-1, 8), axis=1, bitorder='little').reshape(-1)
+
+
+def unpack_mask(bits, shape):
+  return np.unpackbits(np.asarray(bits, np.uint8).reshape(-1, 1), axis=1,
+                       bitorder='little').reshape(shape).astype(bool)
+
+
+# ------------------------------------------------------------------ statistics
+def norm_stats(x, row_scale=None):
+  """sums[g][0][c] = sum_r x * row_scale, sums[g][1][c] = sum_r (x * row_scale)^2.  x [g, r, c]
+  integers, row_scale [g * r] signed powers of two in [1/2, 2]."""
+  x = np.asarray(x, dtype=np.float64)
+  g, r, c = x.shape
+  assert_np_lattice(x, 'x', 1.0, 4.0)
+  q = 1.0
+  v = x
+  if row_scale is not None:
+    assert_all_pow2(row_scale, 'row_scale')
+    q = _qmin(row_scale)
+    v = x * np.asarray(row_scale, np.float64).reshape(g, r, 1)
+  return f32(np.stack([assert_exact_colsum(v, 'sum x', q),
+                       assert_exact_colsum(v * v, 'sum x^2', q * q)], axis=1))
+
+
+def reduce_rows(partial, quantum=0.25):
+  """sums[2][c] = sum over rows of partial[rows][2][c]."""
+  p = np.asarray(partial, dtype=np.float64)
+  rows = p.shape[0]
+  return f32(assert_exact_colsum(p.reshape(rows, -1), 'partial rows', quantum).reshape(p.shape[1:]))
+
+
+# ------------------------------------------------------------------ finalize
+# fp32 roundings of the bounded outputs of se3ds_norm_finalize, counted from the documented
+# formula rstd = rsqrt(var + eps) (a hardware estimate within one ulp, refined by one Newton step
+# r (1.5 - 0.5 (var + eps) r r)), scale = gamma * rstd, shift = beta - mean * scale.  All errors
+# are relative to rstd (the subtraction's operands are 1.5 and ~0.5 and its result ~1):
+#   rstd:  var + eps (1), estimate within one ulp (2), two products (2), difference (1),
+#          final product (1)                                                       -> 7
+#   scale: rstd (7) + product with gamma (1; 0 for a power of two)                 -> 8
+#   shift: scale (8, scaled by |mean|) + product (1) + difference (1)              -> 10
+K_RSTD, K_SCALE, K_SHIFT = 7, 8, 10
+
+
+def norm_finalize(sums, count, gamma, beta, eps, momentum, moving_mean=None, moving_var=None,
+                  use_moving=0):
+  """mean = S0 / count, var = S1 / count - mean^2, rstd = 1 / sqrt(var + eps), scale = gamma *
+  rstd, shift = beta - mean * scale; moving <- moving - (moving - batch) * (1 - momentum).
+  Returns a dict; mean, var and the moving statistics are asserted to be exact in fp32 (so they
+  have one legal bit pattern), rstd / scale / shift are float64 with their magnitudes."""
+  sums = np.asarray(sums, dtype=np.float64)
+  g, _, c = sums.shape
+  count = float(f32(count))
+  eps = float(f32(eps))
+  out = {}
+  if use_moving:
+    mean = np.broadcast_to(exact32(moving_mean, 'moving_mean'), (g, c)).copy()
+    var = np.broadcast_to(exact32(moving_var, 'moving_var'), (g, c)).copy()
+    out['moving_mean'], out['moving_var'] = f32(moving_mean), f32(moving_var)
+  else:
+    assert_pow2(count, 'count')
+    mean = exact32(sums[:, 0] / count, 'mean')
+    ex2 = exact32(sums[:, 1] / count, 'S1 / count')
+    var = exact32(ex2 - exact32(mean * mean, 'mean^2'), 'var')
+    if moving_mean is not None:
+      assert g == 1
+      omm = float(exact32(1.0 - float(f32(momentum)), '1 - momentum'))
+      for key, mov, new in (('moving_mean', moving_mean, mean[0]), ('moving_var', moving_var, var[0])):
+        mov = exact32(mov, key)
+        d = exact32(mov - new, key + ' difference')
+        out[key] = f32(exact32(mov - exact32(d * omm, key + ' step'), key + ' update'))
+  ve = var + eps
+  assert np.all(ve > 0)
+  rstd = 1.0 / np.sqrt(ve)
+  gm = np.ones(c) if gamma is None else np.asarray(gamma, np.float64)
+  bt = np.zeros(c) if beta is None else np.asarray(beta, np.float64)
+  scale = rstd * gm
+  prod = mean * scale
+  shift = bt - prod
+  out.update(mean=f32(mean), var=f32(var), ve=ve, rstd=rstd, scale=scale, shift=shift,
+             mag_rstd=np.abs(rstd), mag_scale=np.abs(scale),
+             mag_shift=np.maximum(np.maximum(np.abs(prod), np.abs(bt)), np.abs(shift)))
+  return out
+
+
+def exactly_rounded_share(got, ref):
+  """Share of elements equal to the float64 reference rounded once to fp32."""
+  got = np.asarray(got, np.float32).reshape(-1)
+  return float(np.mean(got == f32(ref).reshape(-1))) if got.size else 1.0
+
+
+# ------------------------------------------------------------------ apply
+def norm_apply(x, scale, shift, res=None, post=None, act=0, alpha=0.0, bf16=False):
+  """y = act(x * scale + shift [+ res]) [+ post]; x, res, post [g, r, c], scale / shift [g, c].
+  Returns (stored y as fp32, packed act_mask of the stored y or None when c % 8 != 0)."""
+  x = np.asarray(x, dtype=np.float64)
+  g, r, c = x.shape
+  assert_np_lattice(x, 'x', 1.0, 4.0)
+  assert_all_pow2(scale, 'scale')
+  assert_np_lattice(shift, 'shift', 1.0, 8.0)
+  q, bound = _qmin(scale), 4.0 * float(np.abs(scale).max()) + 8.0
+  v = x * np.asarray(scale, np.float64).reshape(g, 1, c) + np.asarray(shift, np.float64).reshape(g, 1, c)
+  if res is not None:
+    assert_np_lattice(res, 'res', 1.0, 4.0)
+    v = v + res
+    bound += 4.0
+  if act == 2:
+    q *= min(1.0, float(alpha))
+  v = act_np(v, act, alpha)
+  if post is not None:
+    assert_np_lattice(post, 'post', 1.0, 4.0)
+    v = v + post
+    bound += 4.0
+  assert_any_order(q, bound, 'norm_apply')
+  y = rne_np(exact32(v, 'y'), bf16)
+  return y, (pack_mask(y) if c % 8 == 0 else None)
+
+
+# ------------------------------------------------------------------ backward
+def _dpre(dy, pos, act, alpha):
+  dy = np.asarray(dy, dtype=np.float64)
+  assert_np_lattice(dy, 'dy', 1.0, 2.0)
+  return dy * act_grad_np(pos, act, alpha) if act else dy
+
+
+def _xhat(x, mean, rstd):
+  x = np.asarray(x, dtype=np.float64)
+  g, r, c = x.shape
+  assert_np_lattice(x, 'x', 1.0, 4.0)
+  assert_np_lattice(mean, 'mean', 1.0, 2.0)
+  assert_all_pow2(rstd, 'rstd')
+  return (x - np.asarray(mean, np.float64).reshape(g, 1, c)) * np.asarray(rstd, np.float64).reshape(g, 1, c)
+
+
+def norm_bwd_stats(dy, pos, x, mean, rstd, act=0, alpha=0.0):
+  """sums[g][0][c] = sum dpre, sums[g][1][c] = sum dpre * xhat; dpre = dy * act'(y), pos = y > 0."""
+  d = _dpre(dy, pos, act, alpha)
+  xh = _xhat(x, mean, rstd)
+  qd = min(1.0, float(alpha)) if act == 2 else 1.0
+  return f32(np.stack([assert_exact_colsum(d, 'sum dpre', qd),
+                       assert_exact_colsum(d * xh, 'sum dpre xhat', qd * _qmin(rstd))], axis=1))
+
+
+def norm_bwd_apply(dy, pos, x, mean, rstd, gamma, sums, count, act=0, alpha=0.0, in_act=0,
+                   in_alpha=0.0, bf16=False, sum_row=None, out_row=None, sums_quantum=None):
+  """dx = gamma * rstd * (dpre - S0 / count - xhat * S1 / count) [* act'(x) for in_act]; dres =
+  dpre.  With sum_row / out_row (the ROWS variants): colsum[c] = sum_r rounded dx * sum_row[r] and
+  dx is stored as rounded dx * out_row[r].  Returns dict(dx, dres[, colsum]) of stored values.
+  sums_quantum: lattice of S0 / S1 (default: integer multiples of count)."""
+  x = np.asarray(x, dtype=np.float64)
+  g, r, c = x.shape
+  d = _dpre(dy, pos, act, alpha)
+  xh = _xhat(x, mean, rstd)
+  count = float(f32(count))
+  assert_pow2(count, 'count')
+  sums = np.asarray(sums, dtype=np.float64)
+  qs = count if sums_quantum is None else sums_quantum
+  assert_np_lattice(sums, 'sums', qs)
+  gm = np.ones(c) if gamma is None else np.asarray(gamma, np.float64)
+  assert_all_pow2(gm, 'gamma')
+  s0 = (sums[:, 0] / count).reshape(g, 1, c)
+  s1 = (sums[:, 1] / count).reshape(g, 1, c)
+  gr = (gm.reshape(1, c) * np.asarray(rstd, np.float64).reshape(g, c)).reshape(g, 1, c)
+  dx = gr * (d - s0 - xh * s1)
+  # any rearrangement (the fast kernels evaluate gr * d + (-k1 * x + c0k)): products of subsets
+  # of the factors are multiples of the product of the factors' quanta, and bounded by the
+  # product of their largest magnitudes
+  qd = min(1.0, float(alpha)) if act == 2 else 1.0
+  q = _qmin(gm) * _qmin(rstd) ** 2 * qd * min(1.0, qs / count)
+  ar = float(np.abs(rstd).max())
+  xm = float(np.abs(x).max()) + float(np.abs(np.asarray(mean, np.float64)).max())
+  bound = float(np.abs(gm).max()) * max(ar, 1.0) * (2.0 + float(np.abs(s0).max()) +
+                                                    2.0 * max(ar, 1.0) * xm * float(np.abs(s1).max()) + 1.0)
+  if in_act:
+    assert in_act in (1, 2)
+    if in_act == 2:
+      q *= min(1.0, float(in_alpha))
+    dx = dx * act_grad_np(x > 0, in_act, in_alpha)
+  assert_any_order(q, bound, 'norm_bwd_apply')
+  exact32(dx, 'dx')
+  out = dict(dres=rne_np(exact32(d, 'dres'), bf16))
+  if sum_row is None:
+    out['dx'] = rne_np(dx, bf16)
+    return out
+  assert g == 1 and bf16 and not in_act
+  assert_np_lattice(sum_row, 'sum_row', 1.0, 1.0)
+  assert_all_pow2(out_row, 'out_row')
+  vr = rne_np(dx, True).astype(np.float64)          # rounding to bf16 keeps multiples of q
+  out['colsum'] = f32(assert_exact_colsum(vr[0] * np.asarray(sum_row, np.float64).reshape(r, 1),
+                                          'bias sum of rounded dx', q))
+  out['dx'] = rne_np(exact32(vr * np.asarray(out_row, np.float64).reshape(1, r, 1), 'dx * out_row'), True)
+  return out
+
+
+def cancelling_rows(r, c, seed, free=5, zero_share=0.3):
+  """dy, x, pos [1, r, c] for se3ds_norm_bwd_cg, whose sums come from the data: cancelling row
+  PAIRS (same x, same mask bits, opposite dy) at random positions plus `free` (or free + 1) rows
+  of their own, so S0 and S1 are small integers whatever r is."""
+  rg = rng(seed)
+  nfree = free if (r - free) % 2 == 0 else free + 1
+  nfree = min(nfree, r) if r >= nfree else r
+  if (r - nfree) % 2:
+    nfree += 1
+  half = (r - nfree) // 2
+  order = rg.permutation(r)
+  dy = np.zeros((r, c))
+  x = np.zeros((r, c))
+  pos = np.zeros((r, c), dtype=bool)
+  a, b, f = order[:half], order[half:2 * half], order[2 * half:]
+  dy[a] = small_ints((half, c), seed + 1, -2, 2)
+  dy[b] = -dy[a]
+  x[a] = small_ints((half, c), seed + 2, -2, 2, zero_share)
+  x[b] = x[a]
+  pos[a] = rg.random((half, c)) < 0.5
+  pos[b] = pos[a]
+  dy[f] = small_ints((f.size, c), seed + 3, -2, 2)
+  x[f] = small_ints((f.size, c), seed + 4, -2, 2)
+  pos[f] = rg.random((f.size, c)) < 0.5
+  return dy[None], x[None], pos[None]
+
+
+def affine_bwd(dy, pos, scale, act=0, alpha=0.0, bf16=False):
+  """Inference-mode backward: dx = dpre * scale, dres = dpre."""
+  d = _dpre(dy, pos, act, alpha)
+  g, r, c = d.shape
+  assert_all_pow2(scale, 'scale')
+  dx = exact32(d * np.asarray(scale, np.float64).reshape(g, 1, c), 'dx')
+  return rne_np(dx, bf16), rne_np(d, bf16)
+
+
+def colsum_row_scale(x, sum_row, out_row):
+  """se3ds_colsum_row_scale (bf16): scaled = x * out_row[row], colsum[c] = sum_r x * sum_row[r]."""
+  x = np.asarray(x, dtype=np.float64)
+  r, c = x.shape
+  assert_np_lattice(x, 'x', 1.0, 4.0)
+  assert_all_pow2(out_row, 'out_row')
+  assert_all_pow2(sum_row, 'sum_row')
+  scaled = rne_np(exact32(x * np.asarray(out_row, np.float64).reshape(r, 1), 'scaled'), True)
+  return scaled, f32(assert_exact_colsum(x * np.asarray(sum_row, np.float64).reshape(r, 1), 'colsum',
+                                          _qmin(sum_row)))
+
+
+# ------------------------------------------------------------------ pooling (NHWC)
+def tie_ints(shape, seed, zero_run=0.5):
+  """Integers in [-2, 2] with runs of zeros along W (post-ReLU zeros): ties, whole-window ties
+  included, are frequent."""
+  r = rng(seed)
+  a = r.integers(-2, 3, shape).astype(np.float64)
+  n, h, w, c = shape
+  run = np.repeat(r.random((n, h, (w + 1) // 2, c)) < zero_run, 2, axis=2)[:, :, :w]
+  rows = np.repeat(r.random((n, (h + 1) // 2, 1, c)) < 0.7, 2, axis=1)[:, :h]
+  a[run & rows] = 0.0
+  return a
+
+
+def _windows2(h, w):
+  for oy in range((h + 1) // 2):
+    for ox in range((w + 1) // 2):
+      yield oy, ox, [(sy, sx) for sy in (2 * oy, 2 * oy + 1) for sx in (2 * ox, 2 * ox + 1)
+                     if sy < h and sx < w]
+
+
+def maxpool2x2_fwd(x):
+  """Keras MaxPool2D(2, padding='SAME'): windows clipped at the bottom / right edge."""
+  x = np.asarray(x, dtype=np.float64)
+  n, h, w, c = x.shape
+  y = np.empty((n, (h + 1) // 2, (w + 1) // 2, c))
+  for oy, ox, taps in _windows2(h, w):
+    y[:, oy, ox] = np.max(np.stack([x[:, sy, sx] for sy, sx in taps]), axis=0)
+  return y
+
+
+def maxpool2x2_bwd(dy, x):
+  """TF MaxPoolGrad: the gradient goes to the FIRST maximum in row-major window order
+  (-0.0 == 0.0).  Returns (dx, share of windows that contain a tie for the maximum)."""
+  x = np.asarray(x, dtype=np.float64)
+  dy = np.asarray(dy, dtype=np.float64)
+  n, h, w, c = x.shape
+  dx = np.zeros_like(x)
+  ties = total = 0
+  for oy, ox, taps in _windows2(h, w):
+    v = np.stack([x[:, sy, sx] for sy, sx in taps])           # [taps, n, c]
+    hit = v == v.max(axis=0)
+    first = hit & (np.cumsum(hit, axis=0) == 1)
+    for k, (sy, sx) in enumerate(taps):
+      dx[:, sy, sx] = np.where(first[k], dy[:, oy, ox], 0.0)
+    ties += int((hit.sum(axis=0) > 1).sum())
+    total += hit[0].size
+  return dx, ties / max(total, 1)
+
+
+def _avg_geom(size):
+  o = (size + 1) // 2
+  return o, max((o - 1) * 2 + 3 - size, 0) // 2
+
+
+def _avg_taps(size):
+  o, p = _avg_geom(size)
+  return [[s for s in range(2 * i - p, 2 * i - p + 3) if 0 <= s < size] for i in range(o)]
+
+
+def assert_lattice36(a, name):
+  """Values in 36 * {-3..3}: divisible by every tap count (4, 6, 9) and exact in bf16."""
+  q = np.asarray(a, dtype=np.float64) / 36.0
+  assert np.array_equal(q, np.round(q)) and np.abs(q).max() <= 3, f'{name}: not in 36 * [-3, 3]'
+
+
+def avgpool3s2_fwd(x, bf16=False, lattice36=True):
+  """tf.nn.avg_pool(3, 2, 'SAME'): the divisor is the count of in-bounds taps.  lattice36: x in
+  36 * {-3..3}, every quotient an integer; otherwise plain integers: the exact sum divided once
+  (correctly rounded: float64 quotient -> fp32) and stored."""
+  x = np.asarray(x, dtype=np.float64)
+  n, h, w, c = x.shape
+  if lattice36:
+    assert_lattice36(x, 'x')
+  else:
+    assert_np_lattice(x, 'x', 1.0, 8.0)
+  ty, tx = _avg_taps(h), _avg_taps(w)
+  y = np.empty((n, len(ty), len(tx), c))
+  for oy, ys in enumerate(ty):
+    for ox, xs in enumerate(tx):
+      s = sum(x[:, sy, sx] for sy in ys for sx in xs)       # integers: exact in any order
+      y[:, oy, ox] = s / (len(ys) * len(xs))
+  if lattice36:
+    assert_np_lattice(y, 'y', 1.0, 255.0)
+  return rne_np(y, bf16)
+
+
+def avgpool3s2_bwd(dy, h, w, bf16=False):
+  """dx[s] = sum over the windows that hold s of dy / (taps of that window); dy in 36 * {-3..3}:
+  every quotient is an integer and the sum of up to four of them stays below 256."""
+  dy = np.asarray(dy, dtype=np.float64)
+  assert_lattice36(dy, 'dy')
+  n, _, _, c = dy.shape
+  ty, tx = _avg_taps(h), _avg_taps(w)
+  dx = np.zeros((n, h, w, c))
+  for oy, ys in enumerate(ty):
+    for ox, xs in enumerate(tx):
+      qv = dy[:, oy, ox] / (len(ys) * len(xs))
+      assert np.array_equal(qv, np.round(qv))
+      for sy in ys:
+        for sx in xs:
+          dx[:, sy, sx] += qv
+  assert_np_lattice(dx, 'dx', 1.0, 255.0)
+  return rne_np(dx, bf16)
+
+
+def upsample2x_fwd(x):
+  return np.repeat(np.repeat(np.asarray(x, np.float64), 2, axis=1), 2, axis=2)
+
+
+def upsample2x_bwd(dy, bf16=False):
+  dy = np.asarray(dy, dtype=np.float64)
+  n, h2, w2, c = dy.shape
+  assert_np_lattice(dy, 'dy', 1.0, 8.0)
+  return rne_np(dy.reshape(n, h2 // 2, 2, w2 // 2, 2, c).sum(axis=(2, 4)), bf16)
+
+
+PAD_MODES = {0: 'constant', 1: 'reflect', 2: 'symmetric'}
+
+
+def pad2d(x, pad, mode, wrap_w, value=0.0):
+  """PadLayer: H and W padded by `pad`; mode 0 CONSTANT(value) / 1 REFLECT / 2 SYMMETRIC;
+  wrap_w: W is padded circularly instead."""
+  x = np.asarray(x, dtype=np.float64)
+  kw = dict(constant_values=value) if mode == 0 else {}
+  y = np.pad(x, ((0, 0), (pad, pad), (0, 0), (0, 0)), mode=PAD_MODES[mode], **kw)
+  if wrap_w:
+    return np.pad(y, ((0, 0), (0, 0), (pad, pad), (0, 0)), mode='wrap')
+  return np.pad(y, ((0, 0), (0, 0), (pad, pad), (0, 0)), mode=PAD_MODES[mode], **kw)
+
+
+def copy_channels(src, src_c0, dst, dst_c0, ncopy, dst_bf16):
+  """dst[r, dst_c0 + i] = convert(src[r, src_c0 + i]); the rest of dst is untouched."""
+  out = np.array(dst, dtype=np.float64)
+  out[:, dst_c0:dst_c0 + ncopy] = rne_np(np.asarray(src)[:, src_c0:src_c0 + ncopy], dst_bf16)
+  return out
+
+
+def row_scale(x, scale, bf16=False):
+  x = np.asarray(x, dtype=np.float64)
+  assert_all_pow2(scale, 'scale')
+  return rne_np(exact32(x * np.asarray(scale, np.float64).reshape(-1, 1), 'x * scale'), bf16)
+
+
+def add(a, b, bf16=False):
+  return rne_np(exact32(np.asarray(a, np.float64) + np.asarray(b, np.float64), 'a + b'), bf16)
+
+
+def act_bwd(dy, y, act, alpha, bf16=False):
+  return rne_np(exact32(np.asarray(dy, np.float64) * act_grad_np(np.asarray(y) > 0, act, alpha),
+                        'dx'), bf16)
+
+
+# ------------------------------------------------------------------ partial-conv mask window
+# ratio = kh kw / (cnt + 1e-6) * um: sum (1), quotient (1), product with um in {0, 1} (0) -> 2;
+# bu = (1 - ratio) * um: ratio (2) + difference (1) -> 3; ru = ratio * um = ratio.
+K_RATIO, K_BU = 2, 3
+MASK_EPS = np.float32(1e-6)
+
+
+def mask_window(mask, ho, wo, kh, kw, stride, pad_t, pad_l, wrap_w):
+  """cnt = window sum of the {0, 1} mask (exact), um = clip(cnt, 0, 1), ratio = kh kw / (cnt +
+  1e-6) * um, ru = ratio * um, bu = (1 - ratio) * um.  Returns a dict: um (exact), cnt, the
+  float64 values ratio / ru / bu with their magnitudes, and ratio32 / bu32: the same formula
+  with one fp32 rounding per operation."""
+  m = np.asarray(mask, dtype=np.float64)
+  n, h, w = m.shape
+  assert_np_lattice(m, 'mask', 1.0, 1.0)
+  assert m.min() >= 0
+  cnt = np.zeros((n, ho, wo))
+  for ky in range(kh):
+    for kx in range(kw):
+      for oy in range(ho):
+        sy = oy * stride - pad_t + ky
+        if not 0 <= sy < h:
+          continue
+        for ox in range(wo):
+          sx = ox * stride - pad_l + kx
+          if wrap_w:
+            sx %= w
+          if 0 <= sx < w:
+            cnt[:, oy, ox] += m[:, sy, sx]
+  um = np.clip(cnt, 0.0, 1.0)
+  k = float(kh * kw)
+  ratio = k / (cnt + float(MASK_EPS)) * um
+  bu = (1.0 - ratio) * um
+  den32 = (cnt.astype(np.float32) + MASK_EPS).astype(np.float32)
+  ratio32 = ((np.float32(k) / den32).astype(np.float32) * um.astype(np.float32)).astype(np.float32)
+  bu32 = ((np.float32(1) - ratio32).astype(np.float32) * um.astype(np.float32)).astype(np.float32)
+  return dict(cnt=cnt, um=f32(um), ratio=ratio, ru=ratio * um, bu=bu, ratio32=ratio32, bu32=bu32,
+              mag_ratio=np.abs(ratio), mag_bu=np.maximum(np.maximum(np.abs(ratio), 1.0) * um, np.abs(bu)))

@@ -488,3 +488,202 @@ def test_recip_clamp_and_head_references():
   yo.backward(torch.from_numpy(dy))
   assert rel_err(LT.head_fwd(xr, 0), yo.detach().numpy()) < 1e-15
   assert rel_err(LT.head_bwd(dy, LT.head_fwd(xr, 0), xr, 0), t.grad.numpy()) < 1e-12
+
+
+# =============================================================================================
+# Norm, pooling and pad references: each against an independent statement, on lattice inputs,
+# with `==`; shuffled fp32 sums; and the admissibility of every GPU case.
+
+def _pattern_x(r, c, seed):
+  """x [1, r, c] whose column statistics are lattice values: mean_c + s_c * (+-1 in equal parts),
+  so mean is an integer, var = s^2 and (eps = 0) rstd = 1 / s a power of two."""
+  g = LT.rng(seed)
+  mean = LT.small_ints((c,), seed + 1, -1, 1)
+  s = LT.signed_pow2((c,), seed + 2, (1.0, 2.0), signed=False)
+  pm = np.stack([g.permutation(np.r_[np.ones(r // 2), -np.ones(r // 2)]) for _ in range(c)], axis=1)
+  return (mean + s * pm)[None], mean, 1.0 / s
+
+
+@pytest.mark.parametrize('act', (0, 1, 2))
+def test_norm_references_equal_torch_autograd(act):
+  r, c, alpha = 8, 16, 0.5
+  x, mean, rstd = _pattern_x(r, c, 40 + act)
+  gamma, beta = LT.signed_pow2((c,), 50, (2.0, 4.0)), LT.small_ints((c,), 51, -3, 3)   # scale >= 1
+  res = LT.small_ints((1, r, c), 52, -4, 4)
+  dy = LT.small_ints((1, r, c), 53, -2, 2)
+  # the staged references
+  sums = LT.norm_stats(x)
+  fin = LT.norm_finalize(sums, float(r), gamma, beta, 0.0, 0.5)
+  assert np.array_equal(fin['mean'][0], mean) and np.array_equal(fin['rstd'][0], rstd)
+  y, mask = LT.norm_apply(x, fin['scale'], fin['shift'], res, None, act, alpha)
+  pos = y > 0
+  assert np.array_equal(LT.unpack_mask(mask, y.shape), pos)
+  bs = LT.norm_bwd_stats(dy, pos, x, fin['mean'], fin['rstd'], act, alpha)
+  out = LT.norm_bwd_apply(dy, pos, x, fin['mean'], fin['rstd'], gamma, bs, float(r), act, alpha,
+                          sums_quantum=0.25)
+  # torch CPU autograd of the textbook batch norm, float64
+  xt = torch.tensor(x[0], requires_grad=True)
+  rt = torch.tensor(res[0], requires_grad=True)
+  mu = xt.mean(0)
+  var = ((xt - mu) ** 2).mean(0)
+  pre = torch.tensor(gamma) * (xt - mu) * var.rsqrt() + torch.tensor(beta) + rt
+  yt = pre if act == 0 else (F.relu(pre) if act == 1 else F.leaky_relu(pre, alpha))
+  (yt * torch.tensor(dy[0])).sum().backward()
+  assert np.array_equal(y[0], yt.detach().numpy().astype(np.float32))
+  assert np.array_equal(out['dx'][0], xt.grad.numpy().astype(np.float32))
+  assert np.array_equal(out['dres'][0], rt.grad.numpy().astype(np.float32))
+  # beta / gamma gradients are the two backward sums (gamma's: sum dpre * xhat)
+  assert np.array_equal(bs[0, 0], out['dres'][0].sum(0))
+  # in_act: the producer's derivative is one more factor
+  o2 = LT.norm_bwd_apply(dy, pos, x, fin['mean'], fin['rstd'], gamma, bs, float(r), act, alpha, 2, 0.5,
+                         sums_quantum=0.25)
+  assert np.array_equal(o2['dx'], LT.f32(out['dx'] * np.where(x > 0, 1.0, 0.5)))
+  # inference-mode backward and the moving-statistics form of finalize
+  adx, ares = LT.affine_bwd(dy, pos, fin['scale'], act, alpha)
+  assert np.array_equal(ares, out['dres']) and np.array_equal(adx, LT.f32(out['dres'] * fin['scale'][:, None]))
+  mov = LT.norm_finalize(np.zeros((1, 2, c)), float(r), gamma, beta, 0.0, 0.5, fin['mean'][0], fin['var'][0], 1)
+  assert np.array_equal(mov['scale'], fin['scale']) and np.array_equal(mov['shift'], fin['shift'])
+
+
+def test_rows_variant_equals_separate_passes():
+  """ROWS: what se3ds_row_scale and a column sum over the stored dx would compute."""
+  r, c = 12, 8
+  d = dict(dy=LT.small_ints((1, r, c), 60, -2, 2), x=LT.small_ints((1, r, c), 61, -2, 2),
+           pos=LT.rng(62).random((1, r, c)) < 0.5)
+  mean, rstd = LT.small_ints((1, c), 63, -1, 1), LT.signed_pow2((1, c), 64, (0.5, 1.0))
+  gamma, sums = LT.signed_pow2((c,), 65, (1.0, 2.0)), LT.small_ints((1, 2, c), 66, -1, 1) * 4.0
+  sr, orow = LT.small_ints((r,), 67, 0, 1), LT.signed_pow2((r,), 68)
+  plain = LT.norm_bwd_apply(d['dy'], d['pos'], d['x'], mean, rstd, gamma, sums, 4.0, 2, 0.5, bf16=True)
+  rows = LT.norm_bwd_apply(d['dy'], d['pos'], d['x'], mean, rstd, gamma, sums, 4.0, 2, 0.5, bf16=True,
+                           sum_row=sr, out_row=orow)
+  assert np.array_equal(rows['dx'][0], LT.row_scale(plain['dx'][0], orow, True))
+  assert np.array_equal(rows['colsum'], (plain['dx'][0].astype(np.float64) * sr[:, None]).sum(0).astype(np.float32))
+  scaled, col = LT.colsum_row_scale(d['x'][0], orow, orow)
+  assert np.array_equal(scaled, LT.row_scale(d['x'][0], orow, True))
+  assert np.array_equal(col, (d['x'][0] * orow[:, None]).sum(0).astype(np.float32))
+
+
+@pytest.mark.parametrize('h,w', ((1, 1), (2, 2), (5, 7), (6, 8), (1, 9)))
+def test_pool_references_equal_torch(h, w):
+  n, c = 2, 5
+  x = LT.tie_ints((n, h, w, c), 70 + h)
+  x[(x == 0) & (LT.rng(71).random(x.shape) < 0.3)] = -0.0
+  dy = LT.small_ints((n, (h + 1) // 2, (w + 1) // 2, c), 72, 1, 3)
+  xt = torch.tensor(x).permute(0, 3, 1, 2).contiguous().requires_grad_(True)
+  yt = F.max_pool2d(xt, 2, 2, ceil_mode=True)
+  yt.backward(torch.tensor(dy).permute(0, 3, 1, 2))
+  assert np.array_equal(LT.maxpool2x2_fwd(x), yt.detach().permute(0, 2, 3, 1).numpy())
+  dx, _ = LT.maxpool2x2_bwd(dy, x)
+  assert np.array_equal(dx, xt.grad.permute(0, 2, 3, 1).numpy())
+  # average pool: TF SAME of a 3 x 3 / 2 window = padding 1 on odd sizes, a clipped last window
+  # on even ones; the divisor counts in-bounds taps
+  xa = 36.0 * LT.small_ints((n, h, w, c), 73, -3, 3)
+  da = 36.0 * LT.small_ints(dy.shape, 74, -3, 3)
+  xt = torch.tensor(xa).permute(0, 3, 1, 2).contiguous().requires_grad_(True)
+  yt = F.avg_pool2d(xt, 3, 2, padding=(h % 2, w % 2), ceil_mode=True, count_include_pad=False)
+  yt.backward(torch.tensor(da).permute(0, 3, 1, 2))
+  assert np.array_equal(LT.avgpool3s2_fwd(xa), yt.detach().permute(0, 2, 3, 1).numpy().astype(np.float32))
+  assert np.array_equal(LT.avgpool3s2_bwd(da, h, w), xt.grad.permute(0, 2, 3, 1).numpy().astype(np.float32))
+  xi = LT.small_ints((n, h, w, c), 75, -8, 8)
+  yi = F.avg_pool2d(torch.tensor(xi).permute(0, 3, 1, 2), 3, 2, padding=(h % 2, w % 2), ceil_mode=True,
+                    count_include_pad=False).permute(0, 2, 3, 1).numpy()
+  assert np.array_equal(LT.avgpool3s2_fwd(xi, lattice36=False), yi.astype(np.float32))
+  # nearest upsample and its adjoint
+  xt = torch.tensor(xi).permute(0, 3, 1, 2).contiguous().requires_grad_(True)
+  ut = F.interpolate(xt, scale_factor=2, mode='nearest')
+  du = LT.small_ints((n, 2 * h, 2 * w, c), 76, -2, 2)
+  ut.backward(torch.tensor(du).permute(0, 3, 1, 2))
+  assert np.array_equal(LT.upsample2x_fwd(xi), ut.detach().permute(0, 2, 3, 1).numpy())
+  assert np.array_equal(LT.upsample2x_bwd(du), xt.grad.permute(0, 2, 3, 1).numpy().astype(np.float32))
+
+
+def test_maxpool_gradient_goes_to_first_maximum():
+  x = np.zeros((1, 2, 2, 1))
+  dx, share = LT.maxpool2x2_bwd(np.full((1, 1, 1, 1), 3.0), x)
+  assert share == 1.0 and dx.reshape(-1).tolist() == [3.0, 0.0, 0.0, 0.0]
+  x[0, :, :, 0] = [[-0.0, 0.0], [-1.0, 0.0]]
+  assert LT.maxpool2x2_bwd(np.full((1, 1, 1, 1), 3.0), x)[0].reshape(-1).tolist() == [3.0, 0.0, 0.0, 0.0]
+  x[0, :, :, 0] = [[-1.0, 2.0], [2.0, 2.0]]
+  assert LT.maxpool2x2_bwd(np.full((1, 1, 1, 1), 3.0), x)[0].reshape(-1).tolist() == [0.0, 3.0, 0.0, 0.0]
+
+
+@pytest.mark.parametrize('pad', (1, 3))
+@pytest.mark.parametrize('wrap', (0, 1))
+def test_pad_reference_equals_torch(pad, wrap):
+  x = LT.small_ints((2, 4, 5, 3), 80 + pad, -4, 4)
+  xt = torch.tensor(x).permute(0, 3, 1, 2)
+  for mode, tmode in ((0, 'constant'), (1, 'reflect')):
+    kw = dict(value=1.5) if mode == 0 else {}
+    yt = F.pad(xt, (0, 0, pad, pad), mode=tmode, **kw)
+    yt = F.pad(yt, (pad, pad, 0, 0), mode='circular') if wrap else F.pad(yt, (pad, pad, 0, 0), mode=tmode, **kw)
+    assert np.array_equal(LT.pad2d(x, pad, mode, wrap, 1.5), yt.permute(0, 2, 3, 1).numpy())
+  # SYMMETRIC (torch has none): index -1 - i reads i, index size + i reads size - 1 - i
+  fold = lambda v, size: v if 0 <= v < size else (-v - 1 if v < 0 else 2 * size - 1 - v)
+  y = LT.pad2d(x, pad, 2, wrap, 0.0)
+  for oy in range(4 + 2 * pad):
+    for ox in range(5 + 2 * pad):
+      sx = (ox - pad) % 5 if wrap else fold(ox - pad, 5)
+      assert np.array_equal(y[:, oy, ox], x[:, fold(oy - pad, 4), sx])
+
+
+def test_mask_window_reference():
+  m = LT.binary_mask(2, 12, 10, 90).numpy().astype(np.float64)
+  for k, stride, wrap in ((3, 1, 0), (3, 2, 1), (4, 2, 0), (7, 2, 1)):
+    ho, pt = LT.out_size(12, k, stride, 'SAME')
+    wo, pl = LT.out_size(10, k, stride, 'SAME')
+    ref = LT.mask_window(m, ho, wo, k, k, stride, pt, pl, wrap)
+    cnt = LT.conv_acc(torch.tensor(m, dtype=torch.float32)[..., None], torch.ones(k, k, 1, 1), ho, wo, stride,
+                      pt, pl, wrap)[..., 0].numpy()
+    assert np.array_equal(ref['cnt'], cnt)
+    assert np.array_equal(ref['um'], (cnt > 0).astype(np.float32))
+    assert np.all(ref['ratio'][cnt == 0] == 0) and np.all(ref['bu'][cnt == 0] == 0)
+    assert LT.bound_ratio(ref['ratio32'], ref['ratio'], LT.K_RATIO, ref['mag_ratio']) <= 1.0
+    assert LT.bound_ratio(ref['bu32'], ref['bu'], LT.K_BU, ref['mag_bu']) <= 1.0
+
+
+def test_small_references():
+  src = LT.small_ints((5, 13), 95, -1024, 1024) / 256.0
+  dst = np.full((5, 11), 7.0)
+  out = LT.copy_channels(src, 3, dst, 2, 8, True)
+  assert np.array_equal(out[:, 2:10], torch.tensor(src[:, 3:11], dtype=torch.float32).bfloat16().float().numpy())
+  assert np.all(out[:, :2] == 7) and np.all(out[:, 10:] == 7)
+  a, b = LT.small_ints((9,), 96, -4, 4, 0.3), LT.small_ints((9,), 97, -4, 4)
+  assert np.array_equal(LT.add(a, b), (a + b).astype(np.float32))
+  at = torch.tensor(a, requires_grad=True)
+  F.leaky_relu(at, 0.5).backward(torch.tensor(b))
+  # the derivative is taken from the OUTPUT's sign, which for a positive slope is the input's
+  assert np.array_equal(LT.act_bwd(b, F.leaky_relu(torch.tensor(a), 0.5).numpy(), 2, 0.5), at.grad.numpy().astype(np.float32))
+
+
+@pytest.mark.parametrize('seed', (0, 1, 2))
+def test_norm_sums_are_order_independent(seed):
+  """The reductions of the largest GPU cases, accumulated in fp32 in a random order, equal the
+  float64 sum: order, tiling and the two-stage reduce cannot matter on the chosen ranges."""
+  r = 65573
+  x = LT.small_ints((r,), 110 + seed, -2, 2)
+  rs = LT.signed_pow2((r,), 111 + seed)
+  dy = LT.small_ints((r,), 112 + seed, -2, 2)
+  pos = LT.rng(113 + seed).random(r) < 0.5
+  d = dy * np.where(pos, 1.0, 0.5)
+  xh = (x - 1.0) * 0.5
+  for terms in (x * rs, (x * rs) ** 2, d, d * xh):
+    assert float(LT.shuffled_f32_sum(terms, seed)) == float(terms.sum())
+  part = LT.small_ints((2563,), 114 + seed, -32, 32) * 0.25
+  assert float(LT.shuffled_f32_sum(part, seed)) == float(part.sum())
+  # bias sum of the ROWS variants: bf16-rounded dx on the lattice of 1 / 128, 16391 rows
+  dx = LT.rne_np(LT.small_ints((16391,), 115 + seed, -600, 600) / 128.0, True).astype(np.float64)
+  LT.assert_exact_colsum(dx[:, None], 'rounded dx', 1.0 / 128)
+  assert float(LT.shuffled_f32_sum(dx, seed)) == float(dx.sum())
+
+
+def test_every_gpu_lattice_case_is_admissible():
+  """Builds the inputs of every case of the two GPU modules and runs the references, whose
+  preconditions (lattice membership, sums of magnitudes below 2^24 quanta, fp32-exact
+  intermediates) decide whether a case may be compared bit for bit -- before a GPU sees it."""
+  import test_norm_lattice_gpu as NG
+  import test_pool_pad_lattice_gpu as PG
+  assert NG.build_all() > 800
+  n, mean_share, min_share = PG.build_all()
+  assert n > 150
+  print(f'max-pool windows with a tie for the maximum: mean {mean_share:.3f}, smallest case {min_share:.3f}')
+  assert min_share >= 0.25, f'ties in only {min_share:.2f} of the windows of one case'
