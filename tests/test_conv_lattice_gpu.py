@@ -82,11 +82,16 @@ def p(t):
   return None if t is None else t.data_ptr()
 
 
+def khw(c):
+  """case dict -> (kh, kw): a case may carry its own 'kh' / 'kw', both default to 'k'."""
+  return c.get('kh', c['k']), c.get('kw', c['k'])
+
+
 def geom(c):
   """case dict -> (ho, wo, pad_t, pad_l)."""
-  k, s = c['k'], c.get('stride', 1)
-  ho, pt = LT.out_size(c['h'], k, s, c.get('padding', 'VALID'), c.get('pad', 0))
-  wo, pl = LT.out_size(c['w'], k, s, c.get('padding', 'VALID'), c.get('pad', 0))
+  (kh, kw), s = khw(c), c.get('stride', 1)
+  ho, pt = LT.out_size(c['h'], kh, s, c.get('padding', 'VALID'), c.get('pad', 0))
+  wo, pl = LT.out_size(c['w'], kw, s, c.get('padding', 'VALID'), c.get('pad', 0))
   return ho, wo, c.get('pad_t', pt), c.get('pad_l', pl)
 
 
@@ -97,6 +102,9 @@ def C(cin, cout, k, stride, padding, pad, n, h, w, **kw):
 
 
 def _seed(c, salt):
+  kh, kw = khw(c)
+  if kh != kw:   # (square cases keep the seeds they always had)
+    return hash((c['cin'], c['cout'], c['k'], c['n'], c['h'], c['w'], kh, kw, salt)) % (2 ** 31)
   return hash((c['cin'], c['cout'], c['k'], c['n'], c['h'], c['w'], salt)) % (2 ** 31)
 
 
@@ -143,9 +151,10 @@ def run_fwd(c, dt, stats=False):
   """se3ds_conv2d_fwd / _fwd_stats with the epilogue form c['epi']:
   none | scale | bias | bias_relu | bias_leaky | partial_bias | partial."""
   L, T = _L(), _DT[dt]
-  n, h, w, cin, cout, k, s = c['n'], c['h'], c['w'], c['cin'], c['cout'], c['k'], c.get('stride', 1)
+  n, h, w, cin, cout, s = c['n'], c['h'], c['w'], c['cin'], c['cout'], c.get('stride', 1)
+  kh, kw = khw(c)
   ho, wo, pt, pl = geom(c)
-  x, kern = LT.ternary((n, h, w, cin), _seed(c, 1)), LT.ternary((k, k, cin, cout), _seed(c, 2))
+  x, kern = LT.ternary((n, h, w, cin), _seed(c, 1)), LT.ternary((kh, kw, cin, cout), _seed(c, 2))
   mask, mbin = _mask_args(c, n, h, w, _seed(c, 3))
   epi = c.get('epi', 'none')
   scale = LT.pow2_scale(_seed(c, 4)) if epi in ('scale', 'partial_bias', 'partial', 'bias_leaky') else None
@@ -161,10 +170,10 @@ def run_fwd(c, dt, stats=False):
   out = Guarded((n, ho, wo, cout), T)
   dx, dwt, dm = dev(x, T), dev(wt, T), dev(mask)
   ds, db, da, drb = dev(scale), dev(bias), dev(row_a), dev(row_b)
-  args = [p(dx), p(dwt), out.ptr(), _lib.dtype_code(dx), n, h, w, cin, ho, wo, cout, k, k, s, pt, pl,
+  args = [p(dx), p(dwt), out.ptr(), _lib.dtype_code(dx), n, h, w, cin, ho, wo, cout, kh, kw, s, pt, pl,
           c.get('wrap', 0), p(dm), mbin, p(ds), p(db), p(da), p(drb), act, alpha]
   if stats:
-    rows = L.se3ds_conv2d_fwd_stats_rows(_lib.dtype_code(dx), n, cin, ho, wo, cout, k, k, s,
+    rows = L.se3ds_conv2d_fwd_stats_rows(_lib.dtype_code(dx), n, cin, ho, wo, cout, kh, kw, s,
                                          int(mask is not None), mbin)
     assert rows > 0, f'{what}: no fused statistics path'
     st = Guarded((rows, 2, cout), torch.float32)
@@ -194,9 +203,10 @@ def run_dgrad(c, dt):
   """se3ds_conv2d_dgrad / _dgrad_acc with c['epi']: none | scale | row_a | bias | bias_relu;
   c['acc']: integer addend; c['row_scale']: dy row scale."""
   L, T = _L(), _DT[dt]
-  n, h, w, cin, cout, k, s = c['n'], c['h'], c['w'], c['cin'], c['cout'], c['k'], c.get('stride', 1)
+  n, h, w, cin, cout, s = c['n'], c['h'], c['w'], c['cin'], c['cout'], c.get('stride', 1)
+  kh, kw = khw(c)
   ho, wo, pt, pl = geom(c)
-  dy, kern = LT.ternary((n, ho, wo, cout), _seed(c, 11)), LT.ternary((k, k, cin, cout), _seed(c, 2))
+  dy, kern = LT.ternary((n, ho, wo, cout), _seed(c, 11)), LT.ternary((kh, kw, cin, cout), _seed(c, 2))
   epi = c.get('epi', 'none')
   scale = LT.pow2_scale(_seed(c, 4)) if epi in ('scale', 'row_a') else None
   row_a = LT.pow2_rows(n * h * w, _seed(c, 6)) if epi == 'row_a' else None
@@ -213,7 +223,7 @@ def run_dgrad(c, dt):
   out = Guarded((n, h, w, cin), T, fill=addend)   # the addend may be dx itself
   ddy, dwn = dev(dy, T), dev(wn, T)
   drs, ds, db, da = dev(rs), dev(scale), dev(bias), dev(row_a)
-  args = [p(ddy), p(dwn), out.ptr(), _lib.dtype_code(ddy), n, h, w, cin, ho, wo, cout, k, k, s, pt, pl,
+  args = [p(ddy), p(dwn), out.ptr(), _lib.dtype_code(ddy), n, h, w, cin, ho, wo, cout, kh, kw, s, pt, pl,
           c.get('wrap', 0), p(drs), p(ds), p(db), p(da), act, alpha]
   if addend is not None:
     _lib.check(L.se3ds_conv2d_dgrad_acc(*args, out.ptr(), _lib.stream()), what)
@@ -279,20 +289,21 @@ def run_wgrad(c, dt, launches=2):
   """se3ds_conv2d_wgrad: c['mask'], c['row_scale'], c['out_scale'], c['acc'] (accumulate = 1 onto an
   integer prior).  Returns the routes of the main kernel and of the split reduction."""
   L, T = _L(), _DT[dt]
-  n, h, w, cin, cout, k, s = c['n'], c['h'], c['w'], c['cin'], c['cout'], c['k'], c.get('stride', 1)
+  n, h, w, cin, cout, s = c['n'], c['h'], c['w'], c['cin'], c['cout'], c.get('stride', 1)
+  kh, kw = khw(c)
   ho, wo, pt, pl = geom(c)
   x, dy, mask, mbin, rs = _wgrad_inputs(c, dt)
   osc = LT.pow2_scale(_seed(c, 16)) if c.get('out_scale') else None
-  prior = LT.prior_grad((k, k, cin, cout), _seed(c, 17)) if c.get('acc') else None
-  exp = _memo('wgrad', c, lambda: LT.conv2d_wgrad(x, dy, (k, k, cin, cout), s, pt, pl, c.get('wrap', 0),
+  prior = LT.prior_grad((kh, kw, cin, cout), _seed(c, 17)) if c.get('acc') else None
+  exp = _memo('wgrad', c, lambda: LT.conv2d_wgrad(x, dy, (kh, kw, cin, cout), s, pt, pl, c.get('wrap', 0),
                                                   mask, rs, osc, prior))
   what = f'wgrad {dt} {c}'
-  out = Guarded((k, k, cin, cout), torch.float32, fill=prior)
-  wsb = L.se3ds_conv2d_wgrad_workspace_bytes(n, ho, wo, cin, cout, k, k)
+  out = Guarded((kh, kw, cin, cout), torch.float32, fill=prior)
+  wsb = L.se3ds_conv2d_wgrad_workspace_bytes(n, ho, wo, cin, cout, kh, kw)
   ws = Guarded((wsb // 4 + 1,), torch.float32)
   dx, ddy, dm, drs, dos = dev(x, T), dev(dy, T), dev(mask), dev(rs), dev(osc)
   _lib.check(L.se3ds_conv2d_wgrad(p(dx), p(ddy), out.ptr(), _lib.dtype_code(dx), n, h, w, cin, ho, wo,
-                                  cout, k, k, s, pt, pl, c.get('wrap', 0), p(dm), mbin, p(drs), p(dos),
+                                  cout, kh, kw, s, pt, pl, c.get('wrap', 0), p(dm), mbin, p(drs), p(dos),
                                   int(prior is not None), ws.ptr(), wsb, _lib.stream()), what)
   routes = last_routes(launches)
   LT.assert_bit_equal(out.result(what), exp, what, 'hwio')

@@ -677,13 +677,107 @@ def test_norm_sums_are_order_independent(seed):
 
 
 def test_every_gpu_lattice_case_is_admissible():
-  """Builds the inputs of every case of the two GPU modules and runs the references, whose
+  """Builds the inputs of every case of the GPU modules and runs the references, whose
   preconditions (lattice membership, sums of magnitudes below 2^24 quanta, fp32-exact
   intermediates) decide whether a case may be compared bit for bit -- before a GPU sees it."""
   import test_norm_lattice_gpu as NG
   import test_pool_pad_lattice_gpu as PG
+  import test_inception_lattice_gpu as IG
   assert NG.build_all() > 800
   n, mean_share, min_share = PG.build_all()
   assert n > 150
   print(f'max-pool windows with a tie for the maximum: mean {mean_share:.3f}, smallest case {min_share:.3f}')
   assert min_share >= 0.25, f'ties in only {min_share:.2f} of the windows of one case'
+  # the evaluator's convolutions: ternary operands, |acc| ~ 0.67 sqrt(K) <= 42 at K = 3*3*448
+  # against the 256-quantum limit of bf16, so the share of elements in which a unit error could
+  # round away is about 0 (printed per case; the cap LT.MAX_INVISIBLE is asserted per case)
+  n, worst = IG.build_all()
+  assert n > 120
+  print(f'evaluator lattice cases: {n}, largest invisible bf16 share {100 * worst:.4f} %')
+  assert worst <= LT.MAX_INVISIBLE
+
+
+# =============================================================================================
+# Non-square kernels (the Inception evaluator's 1x7 / 7x1 / 1x3 / 3x1 layers)
+
+def _tap_loop(x, w, pad_t, pad_l, decode=None):
+  """Stride-1 same-size convolution as a direct float64 tap loop over the linear tap index t;
+  decode(t, kh, kw) -> (ky, kx), by default the row-major order of the HWIO kernel."""
+  x, w = np.asarray(x, np.float64), np.asarray(w, np.float64)
+  n, h, wd, cin = x.shape
+  kh, kw, _, cout = w.shape
+  decode = decode or (lambda t, kh, kw: (t // kw, t % kw))
+  wlin = w.reshape(kh * kw, cin, cout)
+  y = np.zeros((n, h, wd, cout))
+  for t in range(kh * kw):
+    ky, kx = decode(t, kh, kw)
+    for oy in range(h):
+      sy = oy - pad_t + ky
+      if not 0 <= sy < h:
+        continue
+      for ox in range(wd):
+        sx = ox - pad_l + kx
+        if 0 <= sx < wd:
+          y[:, oy, ox] += x[:, sy, sx] @ wlin[t]
+  return y
+
+
+def _swapped_decode(t, kh, kw):
+  """A gather that uses kh where it means kw."""
+  return t // kh, t % kh
+
+
+@pytest.mark.parametrize('kh,kw', [(1, 7), (7, 1), (1, 3), (3, 1)])
+def test_nonsquare_reference_equals_a_tap_loop(kh, kw):
+  n, h, w, cin, cout = 2, 9, 11, 5, 4
+  pt, pl = (kh - 1) // 2, (kw - 1) // 2
+  assert (pt, pl) in ((0, 3), (3, 0), (0, 1), (1, 0))
+  x, kern = LT.ternary((n, h, w, cin), 3 * kh + kw), LT.ternary((kh, kw, cin, cout), 5 * kh + kw)
+  got = LT.conv_acc(x, kern, h, w, 1, pt, pl)
+  assert np.array_equal(got.numpy().astype(np.float64), _tap_loop(x, kern, pt, pl))
+  # the weight operand's K order is the tap loop's linear index
+  wt, wn = LT.weight_operands(kern)
+  assert torch.equal(wn.reshape(kh * kw, cin, cout), kern.reshape(kh * kw, cin, cout))
+  # and the gradients are those of the same loop (autograd of the float64 restatement)
+  dy = LT.ternary((n, h, w, cout), 7)
+  dx, dw = LT.conv2d_grads(x, kern, dy, 1, pt, pl)
+  xo = x.double().requires_grad_(True)
+  ko = kern.double().requires_grad_(True)
+  xp = F.pad(xo.permute(0, 3, 1, 2), (pl, kw - 1 - pl, pt, kh - 1 - pt))
+  F.conv2d(xp, ko.permute(3, 2, 0, 1)).permute(0, 2, 3, 1).mul(dy.double()).sum().backward()
+  assert torch.equal(dx.double(), xo.grad) and torch.equal(dw.double(), ko.grad)
+
+
+def test_exchanged_kh_kw_is_flagged_bit_for_bit_but_not_by_the_pooled_criterion():
+  """A 1x7 'same' layer (pads 0, 3) whose gather decodes the taps with kh and kw exchanged reads
+  seven pixels down a column instead of along a row.  Bit for bit, nearly every element differs and
+  the comparator says where.  The evaluator's own check (tests/test_inception_gpu.py: max|a - b| /
+  max|b| <= 1e-4 on the POOLS, the mean over the pixels of the last map) sees the output only after
+  that mean, and a convolution's pixel sum is sum_t w_t * (sum of the pixels tap t reads): on an
+  input whose support stays clear of the border both decodes read every pixel once per tap, the
+  sums agree exactly and the criterion reports nothing (operands in {0, 1}, so the ReLU is inert)."""
+  n, h, w, cin, cout = 2, 17, 13, 6, 8
+  x = LT.ternary((n, h, w, cin), 41).abs()
+  x[:, :6] = 0          # rows the exchanged decode (sy = oy + t) does not reach from every output row
+  x[:, :, :3] = 0       # columns the true decode (sx = ox - 3 + t) does not reach
+  x[:, :, w - 3:] = 0
+  kern = LT.ternary((1, 7, cin, cout), 42).abs()
+  bias = LT.bias_ints(cout, 43).abs()
+  good, _, _ = LT.conv2d_fwd(x, kern, h, w, 1, 0, 3, bias=bias, act=1)
+  assert np.array_equal(good.numpy(), _tap_loop(x, kern, 0, 3) + bias.numpy())
+  bad = torch.from_numpy(np.maximum(_tap_loop(x, kern, 0, 3, _swapped_decode) + bias.numpy(), 0)).float()
+  for dt_round in (LT.rne_bf16, lambda t: t):
+    r = LT.mismatch_report(dt_round(bad), dt_round(good))
+    assert r is not None and 'elements differ' in r, r
+    with pytest.raises(AssertionError):
+      LT.assert_bit_equal(dt_round(bad), dt_round(good), 'exchanged kh / kw')
+  differing = float((bad != good).float().mean())
+  pools_good, pools_bad = good.double().mean((1, 2)).numpy(), bad.double().mean((1, 2)).numpy()
+  e = rel_err(pools_bad, pools_good)
+  print(f'exchanged kh / kw: {100 * differing:.1f} % of the elements differ; pooled rel_err {e:.3g}')
+  assert differing > 0.3 and pools_good.std() > 0
+  assert e <= TOL_F32OUT       # the evaluator's whole-output criterion passes the wrong gather
+  # on a 7x1 kernel the same slip reads along the row instead
+  k71 = LT.ternary((7, 1, cin, cout), 44)
+  xs = LT.ternary((n, h, w, cin), 45)
+  assert LT.mismatch_report(_tap_loop(xs, k71, 3, 0, _swapped_decode), LT.conv_acc(xs, k71, h, w, 1, 3, 0)) is not None
