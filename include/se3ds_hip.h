@@ -727,6 +727,59 @@ int se3ds_png_inflate(const uint8_t* buf, int64_t buf_bytes, uint8_t* workspace,
 int se3ds_png_inflate_fields(void);
 int se3ds_png_inflate_ring_bytes(void);
 
+/* One uint8 image sheet from a batch of float images -- utils/image_grid.py:24-51 (get_grid_image:
+ * tf.cast(x * 255.0, tf.uint8), then images_to_grid).  csrc/png_encode.hip.
+ * src: (n, h, w, c) F32 / BF16, c 1 or 3.  out: uint8 (ny * h, nx * w, out_c), out_c 1 or 3; tile i
+ * = image i goes to sheet row i / nx, column i % nx, ny * nx <= n; a 1-channel source is replicated
+ * into 3 output channels (the reference tiles depth and masks, trainers/gan_manager.py:560-567).
+ * Value: x * 255.0f in fp32 (a bf16 source is widened first), truncated toward zero, saturated to
+ * [0, 255], NaN -> 0.  This is NOT convert_image_dtype's x * 255.5 (se3ds_quantize expresses that).
+ * BADSHAPE: sizes < 1, c or out_c outside {1, 3}, c 3 with out_c 1, ny * nx > n. */
+int se3ds_grid_quantize(const void* src, int dtype, int n, int h, int w, int c, int ny, int nx,
+                        int out_c, uint8_t* out, void* stream);
+
+/* PNG filtering + zlib deflate of many uint8 images in two launches -- what a TensorBoard image
+ * summary (utils/logger.py:66-71) and the roll-out PNGs (trainers/gan_manager.py:274-296) need
+ * between the pixels and the file.  csrc/png_encode.hip, encoder in csrc/deflate_core.h.
+ * table: device int64 [n][se3ds_png_encode_fields() = 8] = device pointer of the image (height x
+ * row_bytes bytes, dense), height, row_bytes, bytes per pixel (1 or 3), filter (0..4: that PNG
+ * filter type on every row; 5: adaptive, per row the type with the smallest sum of
+ * |int8(residual)|, ties to the lowest type), index of the image's first strip, byte offset of the
+ * image's stream in out, byte offset of the image's first slot behind the workspace's strip records.
+ * An image is cut into strips of max(1, 65535 / (1 + row_bytes)) rows, one wavefront each; with S
+ * strips it takes S slots of (10 + min(rows per strip, height) x (1 + row_bytes)) bytes rounded up to 8, and
+ * 10 S + height x (1 + row_bytes) bytes of out.  The last three fields are running sums of these
+ * over the rows in front, starting at 0.  Mixed geometries share the launch.
+ * A strip becomes one dynamic-Huffman block over literals and distance-1 runs (length 3..258,
+ * greedy; code lengths limited to 15 bits; the code-length code is fixed: 0..15 at 4 bits; one
+ * distance code) or, when that would not be smaller, one stored block; an empty stored block ends
+ * it on a byte boundary, with BFINAL on the image's last strip.  No strip exceeds 10 bytes + its
+ * filtered bytes.  The second launch packs the strips of every image densely at its offset in out
+ * and writes sizes_dev: uint32 [n][2] = bytes of the image's deflate stream, Adler-32 of its
+ * filtered bytes.  The caller frames it: 78 01 + stream + Adler-32 big-endian.  Bytes of out past
+ * an image's size are not written.
+ * workspace: device, 16-byte aligned, at least se3ds_png_encode_workspace_bytes(host_table, n)
+ * bytes (0: the table is not valid); out: at least se3ds_png_encode_out_bytes(host_table, n).
+ * host_table: the HOST copy of the table, validated here before anything runs (BADSHAPE: n < 1 or
+ * > 65535, a null pointer, height < 1, row_bytes not a multiple of the bytes per pixel, a filter
+ * above 5, running sums that are not the ones above, an out buffer that is too small; UNSUPPORTED:
+ * row_bytes above se3ds_png_encode_max_row_bytes(); WORKSPACE: a workspace that is too small).
+ * phases: 3 = both launches, what callers pass; 1 = the strips only, 2 = the packing only, on a
+ * workspace that phase 1 filled for the same table (tools/png_encode_bench.py times them apart).
+ * Both launches on `stream`, no host synchronisation, no atomics, integer arithmetic: the output
+ * is the same bytes on every run. */
+int se3ds_png_encode(const int64_t* table, const int64_t* host_table, int n, uint8_t* workspace,
+                     int64_t workspace_bytes, uint8_t* out, int64_t out_bytes, uint32_t* sizes_dev,
+                     int phases, void* stream);
+size_t se3ds_png_encode_workspace_bytes(const int64_t* host_table, int n);
+int64_t se3ds_png_encode_out_bytes(const int64_t* host_table, int n);
+int se3ds_png_encode_fields(void);
+int se3ds_png_encode_max_row_bytes(void);
+/* HOST arithmetic, no device work: the Adler-32 of a concatenation from the Adler-32 `a` of its
+ * first part and `b` of its len_b further bytes -- how the second launch folds the strips' sums
+ * (csrc/deflate_core.h adler_combine). */
+uint32_t se3ds_adler32_combine(uint32_t a, uint32_t b, int64_t len_b);
+
 /* CRC-32C (Castagnoli: reflected polynomial 0x82F63B78, init and final xor 0xffffffff; RFC 3720
  * B.4, utils/tf_bundle.crc32c) of n byte ranges of one device buffer in one call -- the checksum of
  * TFRecord frames and of the tensors of a checkpoint bundle.  csrc/crc32c.hip, arithmetic in

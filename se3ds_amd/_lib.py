@@ -55,6 +55,13 @@ _SIGS = {
     'se3ds_png_inflate': (c_int, [c_p, c_i64, c_p, c_i64, c_p, c_int, c_p, c_p]),
     'se3ds_png_inflate_fields': (c_int, []),
     'se3ds_png_inflate_ring_bytes': (c_int, []),
+    'se3ds_grid_quantize': (c_int, [c_p] + [c_int] * 8 + [c_p, c_p]),
+    'se3ds_png_encode': (c_int, [c_p, c_p, c_int, c_p, c_i64, c_p, c_i64, c_p, c_int, c_p]),
+    'se3ds_png_encode_workspace_bytes': (c_sz, [c_p, c_int]),
+    'se3ds_png_encode_out_bytes': (c_i64, [c_p, c_int]),
+    'se3ds_png_encode_fields': (c_int, []),
+    'se3ds_png_encode_max_row_bytes': (c_int, []),
+    'se3ds_adler32_combine': (ctypes.c_uint32, [ctypes.c_uint32, ctypes.c_uint32, c_i64]),
     'se3ds_crc32c_multi': (c_int, [c_p, c_i64, c_p, c_p, c_int, c_p, c_p, c_sz, c_p]),
     'se3ds_crc32c_workspace_bytes': (c_sz, [c_i64, c_int]),
     'se3ds_crc32c_fields': (c_int, []),

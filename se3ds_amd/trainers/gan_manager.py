@@ -233,6 +233,10 @@ def _to_uint8(x: torch.Tensor) -> np.ndarray:
 class GANManager(abc.ABC):
   """Constructor surface of the reference (:98-167)."""
 
+  # 'host' | 'device': who encodes the roll-out PNGs of test() -- zlib on the host, frame by frame,
+  # or utils/png.encode_png_batch, all frames of a checkpoint in one batch
+  png_encoder = 'host'
+
   def __init__(self, strategy, model_dir: str = '', image_size: int = 128, seed: int = 1,
                optimizer_type: str = 'adam', beta1: float = 0.0, beta2: float = 0.999,
                g_lr: float = 0.0002, d_lr: float = 0.0002, train_batch_size: int = 128,
@@ -341,8 +345,12 @@ class GANManager(abc.ABC):
         self.train_d(input_list[i])
       self.train_g_d(input_list[-1])
 
-  def train(self, train_ds=None, num_train_steps=None):
-    """Host loop of the reference (:387-423) minus logging / checkpoint files."""
+  def train(self, train_ds=None, num_train_steps=None, logger=None, display_batch=None):
+    """Host loop of the reference (:387-423) minus the checkpoint files.  logger: a
+    utils/logger.UniversalLogger; the metrics go to it as scalars at every log_every_steps.  With a
+    display_batch as well (a trajectory batch, what _get_image_grid takes) the nine image grids of
+    its roll-out go out under the prefix 'train' where the reference saves a checkpoint and logs
+    them (:415-420).  Without a logger nothing is written."""
     self.global_batch_size = self.train_batch_size
     if not hasattr(self, 'generator'):
       self._create_obj()
@@ -355,8 +363,15 @@ class GANManager(abc.ABC):
     for step in range(self.global_step, num_train_steps, self.num_batched_steps):
       self.train_cluster(self.num_batched_steps)
       if step % self.log_every_steps < self.num_batched_steps:
-        self._save_metrics_to_dict()
+        result_dict = self._save_metrics_to_dict()
+        if logger is not None:
+          logger.log_scalars(step, **result_dict)
         self._reset_metrics()
+      if logger is not None and display_batch is not None and step > self.num_batched_steps and (
+          step % self.save_every_steps < self.num_batched_steps):
+        image_dict, _ = self._get_image_dict(self._get_image_grid(display_batch), display_batch,
+                                             'train')
+        logger.log_images(step, **image_dict)
       self.global_step += self.num_batched_steps
 
   def _reset_metrics(self):
@@ -378,7 +393,7 @@ class GANManager(abc.ABC):
     generator, roll a trajectory out autoregressively -- project the memory, generate, feed the
     frame back (utils/eval_metric.generated_rollout; unprojection with void_class 0 as :536-539
     does).  inputs: image (N,T,H,W,3), depth (N,T,H,W,1), position (N,T,3), depth_scale (N,).
-    Returns {mode: RolloutOutput}; composing / writing the TensorBoard grid stays out of scope."""
+    Returns {mode: RolloutOutput}; _get_image_dict composes the TensorBoard grids from it."""
     from se3ds_amd.utils import eval_metric
     res = {}
     for mode in modes:
@@ -387,6 +402,39 @@ class GANManager(abc.ABC):
                                                 predict_depth=self.predict_depth,
                                                 unproject_void_class=0)
     return res
+
+  def _get_image_dict(self, rollouts, inputs, name_prefix):
+    """The second half of the reference's `_get_image_grid` (:558-617): the nine image grids of a
+    roll-out -- rollouts = _get_image_grid(inputs), both modes -- as {name_prefix_<family>: uint8
+    (1, ny*H, nx*W, 3) device tensor}, and output_dict as :611-616.  Frames are concatenated along
+    the batch in frame order; depth and masks fill three channels."""
+    from se3ds_amd.utils import image_grid
+    normal, ema = rollouts['normal'], rollouts['ema']
+    frames = range(self.eval_seq_len)
+
+    def cat(tensors):
+      return torch.cat([t if t.dtype in (torch.float32, torch.bfloat16) else t.float()
+                        for t in tensors], dim=0)
+
+    pred_depth, ema_pred_depth = cat(normal.pred_depth), cat(ema.pred_depth)
+    families = [
+        ('_raw_generated', cat(normal.generated)),
+        ('_ema_generated', cat(ema.generated)),
+        ('_pred_depth', pred_depth),
+        ('_ema_pred_depth', ema_pred_depth),
+        ('_real_img', cat([inputs['image'][:, k] for k in frames])),
+        ('_real_depth', cat([inputs['depth'][:, k] for k in frames])),
+        ('_projected', cat(normal.projected)),
+        ('_blur_bbox', torch.zeros_like(pred_depth)),   # the video branch feeds zeros (:494)
+        ('_proj_mask', cat(normal.proj_mask)),
+    ]
+    image_dict = {}
+    for suffix, x in families:
+      image_dict.update(image_grid.get_grid_image_dict(x, self.show_num, self.strategy,
+                                                       name_prefix + suffix, out_c=3))
+    output_dict = {'ema_generated_image': cat(ema.generated),
+                   'ema_pred_depth': ema_pred_depth.expand(-1, -1, -1, 3)}
+    return image_dict, output_dict
 
   def _score_file(self):
     return os.path.join(self.model_dir, f'scores_{self.test_split}.csv')
@@ -439,6 +487,26 @@ class GANManager(abc.ABC):
   def _save_rollout_images(self, rollout, step):
     """images/<split>/<step>/<frame>/<example>_{rgb,depth}.png of the EMA roll-out (:274-296)."""
     root = os.path.join(self.model_dir, 'images', self.test_split, str(step))
+    if self.png_encoder not in ('host', 'device'):
+      raise ValueError(f"png_encoder: 'host' or 'device', got {self.png_encoder!r}")
+    if self.png_encoder == 'device':
+      # the same pixels: _to_uint8's x * 255.5, truncated, saturated, as se3ds_quantize expresses it
+      # (one fp32 product, the division by 1 exact); every frame of the checkpoint in one batch
+      from se3ds_amd.models.models import _quantize
+      from se3ds_amd.utils import png
+      paths, images = [], []
+      for suffix, frames in (('rgb', rollout.generated), ('depth', rollout.pred_depth)):
+        for frame_idx, frame in enumerate(frames):
+          frame_dir = os.path.join(root, str(frame_idx))
+          os.makedirs(frame_dir, exist_ok=True)
+          pixels = _quantize(frame.detach().float(), torch.uint8, mul=255.5, div=1.0, lo=0.0, hi=255.0)
+          for example_idx in range(pixels.shape[0]):
+            paths.append(os.path.join(frame_dir, f'{example_idx}_{suffix}.png'))
+            images.append(pixels[example_idx])
+      for path, data in zip(paths, png.encode_png_batch(images)):
+        with open(path, 'wb') as f:
+          f.write(data)
+      return
     for suffix, frames in (('rgb', rollout.generated), ('depth', rollout.pred_depth)):
       for frame_idx, frame in enumerate(frames):
         frame_dir = os.path.join(root, str(frame_idx))
@@ -448,9 +516,11 @@ class GANManager(abc.ABC):
           with open(os.path.join(frame_dir, f'{example_idx}_{suffix}.png'), 'wb') as f:
             f.write(_encode_png(pixels[example_idx]))
 
-  def test(self, eval_examples=None, checkpoints=None, unit_test: bool = False, inception=None):
-    """The evaluation loop of the reference (:233-322) minus TensorBoard and the polling task
-    manager.  eval_examples: parsed trajectory examples (what R2RVideoDataset.input_fn takes: a
+  def test(self, eval_examples=None, checkpoints=None, unit_test: bool = False, inception=None,
+           logger=None):
+    """The evaluation loop of the reference (:233-322) minus the polling task manager.  logger: a
+    utils/logger.UniversalLogger; per checkpoint the row's values go to it as scalars and the nine
+    image grids of the display batch's roll-out under the prefix test_split (:241,320-321).  eval_examples: parsed trajectory examples (what R2RVideoDataset.input_fn takes: a
     sequence of per-example dicts, or a callable returning a fresh iterator); TFRecord parsing
     stays outside.  checkpoints: .npz paths (save_checkpoint files); None: every ckpt-<step>.npz
     under model_dir that has no row in scores_<test_split>.csv yet, in step order.  unit_test:
@@ -489,8 +559,9 @@ class GANManager(abc.ABC):
     for checkpoint_path, step in zip(checkpoints, steps):
       if not unit_test:
         self.restore_checkpoint(checkpoint_path)
-      self._save_rollout_images(self._get_image_grid(self.display_batch, modes=('ema',))['ema'],
-                                step)
+      rollouts = self._get_image_grid(self.display_batch,
+                                      modes=('ema',) if logger is None else ('normal', 'ema'))
+      self._save_rollout_images(rollouts['ema'], step)
       fid, _, rmse = metric.calculate_fid_score(self.generator)
       ema_fid, _, ema_rmse = metric.calculate_fid_score(self.ema_generator)
       result = {}
@@ -498,6 +569,10 @@ class GANManager(abc.ABC):
         for k, v in (('fid', fid), ('ema_fid', ema_fid), ('rmse', rmse), ('ema_rmse', ema_rmse)):
           result[f'{self.test_split}/eval_image/{k}@{i}'] = v[i]
       rows.append(self._add_eval_result(checkpoint_path, step, result))
+      if logger is not None:
+        logger.log_scalars(step, **{k: float(rows[-1][k]) for k in result})   # as the row has them
+        image_dict, _ = self._get_image_dict(rollouts, self.display_batch, self.test_split)
+        logger.log_images(step, **image_dict)
     return rows
 
   # -------------------------------------------------------------------------- checkpoint

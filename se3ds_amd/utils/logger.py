@@ -1,0 +1,60 @@
+"""The reference's utils/logger.UniversalLogger without TensorFlow: scalars and image grids go to
+a TensorBoard event file (utils/tf_events.py) and, for scalars, to the log.  Images are PNG-encoded
+on the device in one batch per call (utils/png.encode_png_batch), or on the host for NumPy arrays."""
+import logging
+from typing import Callable, Optional
+
+import numpy as np
+
+from se3ds_amd.utils import png, tf_events
+
+
+class UniversalLogger:
+  """Constructor surface of the reference (:36-55) plus `encoder`: 'device' takes uint8 device
+  tensors, 'host' NumPy arrays (a CPU-only process can write summaries)."""
+
+  def __init__(self, workdir: str, step: int, num_train_steps: Optional[int] = None,
+               logging_fn: Optional[Callable[[str], None]] = None, encoder: str = 'device'):
+    if encoder not in ('host', 'device'):
+      raise ValueError(f"encoder: 'host' or 'device', got {encoder!r}")
+    self.summary_writer = tf_events.EventFileWriter(workdir)
+    self.encoder = encoder
+    self._num_train_steps = num_train_steps
+    self._print = logging_fn or logging.info
+    self._steps_per_sec_start_step = step
+
+  def log_scalars(self, step: int, **kwargs):
+    """Log scalars (given as keyword arguments)."""
+    log_msg = ', '.join([f'{k} = {v:.3f}' for k, v in sorted(kwargs.items())])
+    self._print(f'[{step}] {log_msg}')
+    for k, v in sorted(kwargs.items()):
+      self.summary_writer.add_scalar(k, float(v), step)
+    self.summary_writer.flush()
+
+  def log_images(self, step: int, max_outputs: int = 10, **kwargs):
+    """Log images (given as keyword arguments): each value uint8 (k,H,W,C), C 1 or 3.  The first
+    min(k, max_outputs) go out under the tag `name` (k = 1) or `name/image/<i>`, as tf.summary.image
+    names them; all images of the call are encoded in one batch."""
+    tags, images = [], []
+    for name, value in sorted(kwargs.items()):
+      if len(value.shape) != 4:
+        raise ValueError(f'{name}: uint8 (k,H,W,C) expected, got {tuple(value.shape)}')
+      if self.encoder == 'host' and not isinstance(value, np.ndarray):
+        raise ValueError(f"{name}: encoder='host' takes NumPy arrays")
+      count = min(int(value.shape[0]), int(max_outputs))
+      for i in range(count):
+        tags.append(name if value.shape[0] == 1 else f'{name}/image/{i}')
+        images.append(value[i])
+    if not images:
+      return
+    if self.encoder == 'device':
+      files = png.encode_png_batch(images)
+    else:
+      files = [png.encode_png_host(x) for x in images]
+    for tag, x, data in zip(tags, images, files):
+      self.summary_writer.add_image(tag, data, int(x.shape[0]), int(x.shape[1]), step,
+                                    channels=int(x.shape[2]))
+    self.summary_writer.flush()
+
+  def close(self):
+    self.summary_writer.close()

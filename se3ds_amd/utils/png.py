@@ -374,3 +374,168 @@ def decode_png_batch_async(bufs_by_key: Dict[str, Sequence[Union[bytes, PngStrea
     event = torch.cuda.Event()
     event.record()
   return out, PendingDecode(event, status_host, names, streams)
+
+
+# ------------------------------------------------------------------------------ encoding
+ADAPTIVE = 5   # the filter field of se3ds_png_encode: 0..4 = that PNG filter type on every row
+_FILTER_NAMES = {'none': 0, 'sub': 1, 'up': 2, 'average': 3, 'paeth': 4, 'adaptive': ADAPTIVE}
+
+
+def _filter_mode(f) -> int:
+  mode = _FILTER_NAMES.get(f.lower()) if isinstance(f, str) else (int(f) if 0 <= int(f) <= 4 else None)
+  if mode is None:
+    raise ValueError(f"filters: 'adaptive', a PNG filter type 0..4 or its name, got {f!r}")
+  return mode
+
+
+def _filter_modes(filters, n: int) -> List[int]:
+  if isinstance(filters, (list, tuple)):
+    if len(filters) != n:
+      raise ValueError(f'filters: {len(filters)} entries for {n} images')
+    return [_filter_mode(f) for f in filters]
+  return [_filter_mode(filters)] * n
+
+
+def _chunk(tag: bytes, data: bytes) -> bytes:
+  return struct.pack('>I', len(data)) + tag + data + struct.pack('>I', zlib.crc32(tag + data))
+
+
+def png_container(height: int, width: int, channels: int, zlib_stream: bytes) -> bytes:
+  """Signature, IHDR (8-bit grey or RGB, non-interlaced), one IDAT chunk, IEND."""
+  ihdr = struct.pack('>IIBBBBB', width, height, 8, 0 if channels == 1 else 2, 0, 0, 0)
+  return SIGNATURE + _chunk(b'IHDR', ihdr) + _chunk(b'IDAT', zlib_stream) + _chunk(b'IEND', b'')
+
+
+def strip_rows(row_bytes: int) -> int:
+  """Rows per strip of se3ds_png_encode: a strip's filtered bytes fit one stored block."""
+  return max(1, 65535 // (1 + row_bytes))
+
+
+def encode_table(pointers: Sequence[int], geometries: Sequence[Tuple[int, int, int]],
+                 modes: Sequence[int]) -> np.ndarray:
+  """The descriptor table of se3ds_png_encode (include/se3ds_hip.h) for images at device addresses
+  `pointers` with (height, row_bytes, bytes per pixel) `geometries`: int64 (n, 8)."""
+  table = np.zeros((len(pointers), 8), np.int64)
+  strips = out = slots = 0
+  for i, (p, (h, rb, bpp), mode) in enumerate(zip(pointers, geometries, modes)):
+    table[i] = (p, h, rb, bpp, mode, strips, out, slots)
+    per = strip_rows(rb)
+    s = -(-h // per)
+    strips += s
+    out += 10 * s + h * (1 + rb)
+    slots += s * ((10 + min(per, h) * (1 + rb) + 7) & ~7)
+  return table
+
+
+def _check_pixels(shape, dtype, what):
+  if dtype not in (torch.uint8, np.dtype(np.uint8)) or len(shape) != 3 or shape[2] not in (1, 3) or \
+      shape[0] < 1 or shape[1] < 1:
+    raise ValueError(f'{what}: uint8 (H,W,1) or (H,W,3) expected, got {dtype} {tuple(shape)}')
+
+
+def encode_streams(images: Sequence[torch.Tensor], filters='adaptive', fill: int = None
+                   ) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+  """The device half of encode_png_batch: -> (table, sizes, streams).  table: the descriptor table
+  (encode_table); sizes: uint32 (n, 2) = bytes of each image's deflate stream, Adler-32 of its
+  filtered bytes; streams: the downloaded compact buffer, image i's stream at table[i, 6].  fill:
+  the output buffer is set to this byte before the launches (tests look at what stays untouched)."""
+  images = list(images)
+  _lib.require_cuda(*images)
+  dev = images[0].device
+  for x in images:
+    _check_pixels(x.shape, x.dtype, 'encode_png_batch')
+    if x.device != dev:
+      raise ValueError(f'encode_png_batch: a tensor on {x.device} in a batch on {dev}')
+  images = [x.contiguous() for x in images]
+  modes = _filter_modes(filters, len(images))
+  L = _lib.lib()
+  n = len(images)
+  geometries = [(x.shape[0], x.shape[1] * x.shape[2], x.shape[2]) for x in images]
+  table = encode_table([x.data_ptr() for x in images], geometries, modes)
+  assert table.shape[1] == L.se3ds_png_encode_fields()
+  workspace_bytes = L.se3ds_png_encode_workspace_bytes(table.ctypes.data, n)
+  out_bytes = L.se3ds_png_encode_out_bytes(table.ctypes.data, n)
+  head = (8 * n + 15) & ~15   # the sizes lead the download buffer
+  with torch.cuda.device(dev):
+    staging = torch.from_numpy(table.reshape(-1)).pin_memory()
+    table_dev = staging.to(dev, non_blocking=True)
+    workspace = torch.empty((max(workspace_bytes, 16),), dtype=torch.uint8, device=dev)
+    result = torch.empty((head + out_bytes,), dtype=torch.uint8, device=dev)
+    if fill is not None:
+      result.fill_(fill)
+    rc = L.se3ds_png_encode(_lib.ptr(table_dev), table.ctypes.data, n, _lib.ptr(workspace),
+                            workspace_bytes, _lib.ptr(result) + head, out_bytes, _lib.ptr(result), 3,
+                            _lib.stream())
+    _lib.check(rc, 'se3ds_png_encode')
+    host = torch.empty((head + out_bytes,), dtype=torch.uint8, pin_memory=True)
+    host.copy_(result, non_blocking=True)
+    torch.cuda.current_stream().synchronize()
+  buf = host.numpy()
+  return table, buf[:8 * n].view(np.uint32).reshape(n, 2), buf[head:]
+
+
+def encode_png_batch(images: Sequence[torch.Tensor], filters='adaptive', device=None) -> List[bytes]:
+  """uint8 device tensors (H,W,1|3), any mix of sizes -> their PNG files, encoded on the device:
+  one upload (the descriptor table), se3ds_png_encode's two launches (csrc/png_encode.hip: filter
+  and deflate every strip of every image, one wavefront each; pack the strips), one download (the
+  sizes and the packed streams).  The host adds what has no width: signature, IHDR, the zlib
+  framing of IDAT (78 01 + stream + Adler-32), IEND and the chunk CRCs.
+  filters: 'adaptive' (per row the filter type with the smallest sum of |int8(residual)|), a PNG
+  filter type 0..4 or its name, or a sequence with one of these per image.  device: where the
+  tensors must be (None: where the first one is).  A non-CUDA tensor raises Se3dsHipError:
+  encode_png_host is the CPU encoder."""
+  images = list(images)
+  if not images:
+    return []
+  if device is not None:
+    dev = torch.device(device)
+    for x in images:
+      if x.device.type != dev.type or (dev.index is not None and x.device.index != dev.index):
+        raise ValueError(f'encode_png_batch: a tensor on {x.device}, device={dev}')
+  table, sizes, streams = encode_streams(images, filters)
+  files = []
+  for row, (size, adler) in zip(table, sizes):
+    at, h, rb, bpp = int(row[6]), int(row[1]), int(row[2]), int(row[3])
+    stream = b'\x78\x01' + streams[at:at + int(size)].tobytes() + struct.pack('>I', int(adler))
+    files.append(png_container(h, rb // bpp, bpp, stream))
+  return files
+
+
+def _paeth_predictor(a, b, c):
+  p = a + b - c
+  pa, pb, pc = np.abs(p - a), np.abs(p - b), np.abs(p - c)
+  return np.where((pa <= pb) & (pa <= pc), a, np.where(pb <= pc, b, c))
+
+
+def filter_rows_host(pixels: np.ndarray, mode: int) -> np.ndarray:
+  """uint8 (H,W,C) -> the filtered scan lines uint8 (H, 1 + W*C) under the device encoder's rule."""
+  h, w, c = pixels.shape
+  cur = pixels.reshape(h, w * c).astype(np.int32)
+  left = np.zeros_like(cur)
+  left[:, c:] = cur[:, :-c]
+  up = np.zeros_like(cur)
+  up[1:] = cur[:-1]
+  upleft = np.zeros_like(cur)
+  upleft[:, c:] = up[:, :-c]
+  if mode == ADAPTIVE:
+    res = np.stack([cur, cur - left, cur - up, cur - ((left + up) >> 1),
+                    cur - _paeth_predictor(left, up, upleft)]) & 0xff
+    types = np.argmin(np.where(res < 128, res, 256 - res).sum(axis=2), axis=0)
+    rows = res[types, np.arange(h)]
+  else:
+    pred = (0, left, up, (left + up) >> 1, None)[mode]
+    rows = (cur - (_paeth_predictor(left, up, upleft) if mode == 4 else pred)) & 0xff
+    types = np.full((h,), mode)
+  return np.concatenate([types[:, None], rows], axis=1).astype(np.uint8)
+
+
+def encode_png_host(pixels: np.ndarray, filters='adaptive') -> bytes:
+  """The CPU encoder: the same filters in NumPy, then zlib with Z_RLE (distance-1 matches only,
+  as the device encoder).  The file decodes to the same pixels as encode_png_batch's; its bytes
+  need not be equal."""
+  pixels = np.ascontiguousarray(pixels)
+  _check_pixels(pixels.shape, pixels.dtype, 'encode_png_host')
+  filtered = filter_rows_host(pixels, _filter_mode(filters))
+  z = zlib.compressobj(6, zlib.DEFLATED, 15, 9, zlib.Z_RLE)
+  h, w, c = pixels.shape
+  return png_container(h, w, c, z.compress(filtered.tobytes()) + z.flush())

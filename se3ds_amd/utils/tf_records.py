@@ -136,14 +136,19 @@ def _read_records_device(path: str, batch_bytes: int) -> Iterator[bytes]:
         pending_bytes = 0
 
 
+def frame_record(rec: bytes) -> bytes:
+  """One record as it stands in a file: length, its masked CRC-32C, payload, its masked CRC-32C."""
+  rec = bytes(rec)
+  head = struct.pack('<Q', len(rec))
+  return (head + struct.pack('<I', mask_crc(crc32c(head))) + rec +
+          struct.pack('<I', mask_crc(crc32c(rec))))
+
+
 def write_records(path: str, records: Iterable[bytes]):
   """The inverse of read_records."""
   with open(path, 'wb') as f:
     for rec in records:
-      rec = bytes(rec)
-      head = struct.pack('<Q', len(rec))
-      f.write(head + struct.pack('<I', mask_crc(crc32c(head))) + rec +
-              struct.pack('<I', mask_crc(crc32c(rec))))
+      f.write(frame_record(rec))
 
 
 # ------------------------------------------------------------------------------- Example
