@@ -856,6 +856,82 @@ int se3ds_softmax_rows(const void* x, int dtype, int64_t rows, int c, float* y, 
 int se3ds_feature_moments_accumulate(const float* x, int64_t rows, int c, int64_t* count,
                                      double* sum, double* gram, void* stream);
 
+/* ======================================================================================
+ * Semantic utilities -- utils/utils.py (reference utils/utils.py:23-198).  csrc/semantic.hip,
+ * index arithmetic in csrc/nn_inpaint_core.h.
+ * ====================================================================================== */
+
+/* nearest_neighbor_inpaint (utils/utils.py:179-198): every pixel of image (n, h, w) U8 / I32 / F32
+ * that equals the void class takes the value of the nearest pixel of the same image that does not,
+ * nearest by squared Euclidean distance in pixel units; among equidistant sources the smallest row
+ * wins, within it the smallest column (the reference's argmin over tf.where's row-major list).
+ * Every other pixel is copied.  Values move bit for bit.  void_bits: the void class as the dtype's
+ * bits, zero-extended; equality is == of the dtype (F32: -0.0 equals 0.0, a NaN never matches).
+ * out: (n, h, w) of the same dtype, must not alias image.  indices: NULL, or int32 (n, h, w) that
+ * receives the flat index y * w + x of every pixel's source: its own for a non-void pixel, -1 where
+ * the image has no non-void pixel (such an image is copied unchanged).
+ * workspace: device, 16-byte aligned, at least se3ds_nn_inpaint_workspace_bytes(n, h, w) bytes (0:
+ * the shape is not valid): the row pass's table, an int16 column per pixel.
+ * Two launches on `stream`: the row pass (one workgroup per image row, se3ds_nn_inpaint_row_segment()
+ * columns at a time) and the column pass (se3ds_nn_inpaint_col_tile_rows() rows x 64 lanes per
+ * workgroup; a lane owns one I32 / F32 pixel or four U8 pixels).  phases: 3 = both, what callers
+ * pass; 1 = the row pass only, 2 = the column pass only, on a workspace that phase 1 filled for the
+ * same image (tools/semantic_utils_bench.py times them apart).  Integers only, no atomics, no host
+ * synchronisation: deterministic.
+ * All checks run before the first HIP call.  BADSHAPE: n, h or w < 1, h or w > 16384, n > 65535,
+ * a null or misaligned pointer, phases outside 1..3; BADDTYPE; WORKSPACE: too small. */
+int se3ds_nn_inpaint(const void* image, int dtype, uint32_t void_bits, int n, int h, int w,
+                     void* out, int32_t* indices, void* workspace, size_t workspace_bytes,
+                     int phases, void* stream);
+size_t se3ds_nn_inpaint_workspace_bytes(int n, int h, int w);
+int se3ds_nn_inpaint_row_segment(void);
+int se3ds_nn_inpaint_col_tile_rows(void);
+
+/* Per-frame sums of compute_sequence_iou (utils/utils.py:98-133) over frames x (pixels, channels)
+ * fp32, each frame dense: sums[f][0] = I = sum p * t * s, sums[f][1] = S = sum (p + t) * s, s the
+ * spatial mask fp32 (frames, pixels) of the element's PIXEL (NULL: 1).  Every term is formed in
+ * binary64 as (double)p * (double)t * (double)s and ((double)p + (double)t) * (double)s and added in
+ * binary64.  Two stages: a workgroup per chunk of se3ds_seq_sums_chunk() elements of a frame writes
+ * its pair to the workspace, a second launch adds a frame's pairs in a fixed order.  No atomics: the
+ * same input at the same addresses gives the same bits on every run.  sums: device binary64
+ * (frames, 2).  workspace: device, 8-byte aligned, se3ds_seq_sums_workspace_bytes(frames, pixels *
+ * channels) bytes (0: not a valid shape).  BADSHAPE: a size < 1, pixels * channels > INT32_MAX,
+ * frames * chunks per frame > INT32_MAX, a null or misaligned pointer; WORKSPACE. */
+int se3ds_seq_iou_sums(const float* pred, const float* truth, const float* spatial, int64_t frames,
+                       int64_t pixels, int channels, double* sums, void* workspace,
+                       size_t workspace_bytes, void* stream);
+/* Per-frame sums of compute_sequence_accuracy (utils/utils.py:136-176) over label maps (frames,
+ * pixels) U8 / I32 (both of label_dtype): sums[f][0] = sum [pred == gt] * s, sums[f][1] = sum s.
+ * spatial: NULL (s = 1) or (frames, pixels) of spatial_dtype U8 (also bool) / I32 / F32.  Integer
+ * masks are added as integers (exact below 2^53), an fp32 mask in binary64; stages, workspace
+ * (se3ds_seq_sums_workspace_bytes(frames, pixels)) and reproducibility as above. */
+int se3ds_seq_label_match(const void* pred, const void* gt, int label_dtype, const void* spatial,
+                          int spatial_dtype, int64_t frames, int64_t pixels, double* sums,
+                          void* workspace, size_t workspace_bytes, void* stream);
+size_t se3ds_seq_sums_workspace_bytes(int64_t frames, int64_t elems_per_frame);
+int se3ds_seq_sums_chunk(void);
+/* The (n, t)-sized tail of both metrics, one small launch, all in fp32 after I32 = (float)I and
+ * S32 = (float)S (for IOU_LABELS: (float)(2 S), the S of the one-hot encodings):
+ *   IOU, IOU_LABELS: seq = divide_no_nan(I32 * mask, (S32 - I32) * mask)
+ *   ACCURACY:        seq = divide_no_nan(I32, S32)
+ *   mean = (sum_n divide_no_nan(sum_t seq, sum_t mask)) / n, t = 0..t-1 and n = 0..n-1 in that order.
+ * divide_no_nan(x, y) is 0 where y == 0.  mask fp32 (n, t); seq fp32 (n, t); mean fp32 (1). */
+#define SE3DS_SEQ_IOU 0
+#define SE3DS_SEQ_ACCURACY 1
+#define SE3DS_SEQ_IOU_LABELS 2
+int se3ds_seq_finalize(const double* sums, const float* mask, int n, int t, int mode, float* seq,
+                       float* mean, void* stream);
+
+/* cmap_to_label (utils/utils.py:43-57): labels[p] = the first k with cmap[k] == image[p] in all
+ * three channels, 0 when there is none.  image (pixels, 3) U8 / I32; cmap device int32 (k, 3),
+ * k <= 256; an entry or a pixel with a channel outside 0..255 matches nothing.  labels int32. */
+int se3ds_cmap_to_label(const void* image, int dtype, int64_t pixels, const int32_t* cmap, int k,
+                        int32_t* labels, void* stream);
+/* The gather the other way: out uint8 (pixels, 3) = cmap[labels[p]] (low 8 bits of each channel),
+ * (0, 0, 0) for a label outside [0, k).  labels U8 / I32. */
+int se3ds_label_to_color(const void* labels, int dtype, int64_t pixels, const int32_t* cmap, int k,
+                         uint8_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

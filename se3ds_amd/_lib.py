@@ -85,6 +85,18 @@ _SIGS = {
     'se3ds_global_avg_pool': (c_int, [c_p, c_int, c_int, c_int, c_int, c_p, c_p]),
     'se3ds_softmax_rows': (c_int, [c_p, c_int, c_i64, c_int, c_p, c_p]),
     'se3ds_feature_moments_accumulate': (c_int, [c_p, c_i64, c_int, c_p, c_p, c_p, c_p]),
+    'se3ds_nn_inpaint': (c_int, [c_p, c_int, ctypes.c_uint32, c_int, c_int, c_int, c_p, c_p, c_p, c_sz,
+                                 c_int, c_p]),
+    'se3ds_nn_inpaint_workspace_bytes': (c_sz, [c_int, c_int, c_int]),
+    'se3ds_nn_inpaint_row_segment': (c_int, []),
+    'se3ds_nn_inpaint_col_tile_rows': (c_int, []),
+    'se3ds_seq_iou_sums': (c_int, [c_p, c_p, c_p, c_i64, c_i64, c_int, c_p, c_p, c_sz, c_p]),
+    'se3ds_seq_label_match': (c_int, [c_p, c_p, c_int, c_p, c_int, c_i64, c_i64, c_p, c_p, c_sz, c_p]),
+    'se3ds_seq_sums_workspace_bytes': (c_sz, [c_i64, c_i64]),
+    'se3ds_seq_sums_chunk': (c_int, []),
+    'se3ds_seq_finalize': (c_int, [c_p, c_p, c_int, c_int, c_int, c_p, c_p, c_p]),
+    'se3ds_cmap_to_label': (c_int, [c_p, c_int, c_i64, c_p, c_int, c_p, c_p]),
+    'se3ds_label_to_color': (c_int, [c_p, c_int, c_i64, c_p, c_int, c_p, c_p]),
 }
 
 _lib = None
