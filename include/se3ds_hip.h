@@ -856,6 +856,40 @@ int se3ds_softmax_rows(const void* x, int dtype, int64_t rows, int c, float* y, 
 int se3ds_feature_moments_accumulate(const float* x, int64_t rows, int c, int64_t* count,
                                      double* sum, double* gram, void* stream);
 
+/* ---- The Frechet distance on the device, binary64 throughout.  csrc/frechet.hip. ---- */
+/* C = alpha * A B + diag * I, all row-major n x n binary64, on v_mfma_f64_16x16x4_f64: one
+ * 128 x 128 tile of C per 256-thread workgroup, K staged through LDS 16 at a time, the sum over k
+ * in ascending order inside one accumulator per element; the epilogue rounds alpha * acc, then adds
+ * diag where row == column.  n is arbitrary (1..16384); C must not alias A or B. */
+int se3ds_f64_gemm(const double* a, const double* b, double* c, int n, double alpha, double diag,
+                   void* stream);
+/* The device moments of se3ds_feature_moments_accumulate -> mean[j] = sum[j] / n and the full
+ * symmetric cov[i][j] = (gram[min(i,j)][max(i,j)] - sum[i] sum[j] / n) / (n - 1), n = *count as
+ * binary64, each operation rounded as written (FeatureMoments.mean_cov()).  Only the upper tiles of
+ * gram are read.  *count < 2 gives non-finite values: the caller checks the count. */
+int se3ds_moments_mean_cov(const int64_t* count, const double* sum, const double* gram, int dim,
+                           double* mean, double* cov, void* stream);
+/* tr sqrt(A) (and sqrt(A)) of a symmetric positive semi-definite A (n x n) by the coupled
+ * Newton-Schulz iteration: c = ||A||_F, Y0 = A / c, Z0 = I; T = 1.5 I - 0.5 Z Y, Y <- Y T,
+ * Z <- T Z (three se3ds_f64_gemm products); after iteration k the trace of Y_k is taken and the
+ * iteration stops when |tr Y_k - tr Y_{k-1}| <= tol |tr Y_k|, when the trace is not finite, or after
+ * max_iters (0..1024) iterations.  sqrt(A) = sqrt(c) Y, tr sqrt(A) = sqrt(c) tr Y.  The stop rule
+ * is part of the algorithm: for a singular A, Z grows without bound if the iteration runs on.
+ * Everything is queued on `stream` with no host synchronisation: the trace kernel sets a device flag
+ * and the kernels of the later iterations return at once.  Reductions have a fixed order and no
+ * atomics.  root: n x n, or NULL.  result: device binary64 [4] = tr sqrt(A), iterations taken,
+ * status (SE3DS_SQRT_*), ||A||_F.  A = 0 gives trace 0, a zero root, CONVERGED.  workspace: device,
+ * 8-byte aligned, se3ds_sqrt_trace_workspace_bytes(n) bytes (0: n outside 1..16384). */
+#define SE3DS_SQRT_CONVERGED 0
+#define SE3DS_SQRT_CAP_REACHED 1
+#define SE3DS_SQRT_NONFINITE 2
+size_t se3ds_sqrt_trace_workspace_bytes(int n);
+int se3ds_sqrt_trace(const double* a, int n, int max_iters, double tol, double* root,
+                     void* workspace, size_t workspace_bytes, double* result, void* stream);
+/* out[3] = |mu1 - mu2|^2, tr sigma1, tr sigma2 (device binary64, one workgroup, fixed order). */
+int se3ds_frechet_terms(const double* mu1, const double* mu2, const double* sigma1,
+                        const double* sigma2, int n, double* out, void* stream);
+
 /* ======================================================================================
  * Semantic utilities -- utils/utils.py (reference utils/utils.py:23-198).  csrc/semantic.hip,
  * index arithmetic in csrc/nn_inpaint_core.h.

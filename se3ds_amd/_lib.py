@@ -16,6 +16,7 @@ _DTYPE_CODE = {torch.float32: F32, torch.int32: I32, torch.uint8: U8, torch.bflo
 
 c_int, c_i64, c_f, c_p, c_sz = (ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p,
                                 ctypes.c_size_t)
+c_d = ctypes.c_double
 
 # name -> (restype, argtypes); mirrors include/se3ds_hip.h one to one.
 _SIGS = {
@@ -85,6 +86,11 @@ _SIGS = {
     'se3ds_global_avg_pool': (c_int, [c_p, c_int, c_int, c_int, c_int, c_p, c_p]),
     'se3ds_softmax_rows': (c_int, [c_p, c_int, c_i64, c_int, c_p, c_p]),
     'se3ds_feature_moments_accumulate': (c_int, [c_p, c_i64, c_int, c_p, c_p, c_p, c_p]),
+    'se3ds_f64_gemm': (c_int, [c_p, c_p, c_p, c_int, c_d, c_d, c_p]),
+    'se3ds_moments_mean_cov': (c_int, [c_p, c_p, c_p, c_int, c_p, c_p, c_p]),
+    'se3ds_sqrt_trace_workspace_bytes': (c_sz, [c_int]),
+    'se3ds_sqrt_trace': (c_int, [c_p, c_int, c_int, c_d, c_p, c_p, c_sz, c_p, c_p]),
+    'se3ds_frechet_terms': (c_int, [c_p, c_p, c_p, c_p, c_int, c_p, c_p]),
     'se3ds_nn_inpaint': (c_int, [c_p, c_int, ctypes.c_uint32, c_int, c_int, c_int, c_p, c_p, c_p, c_sz,
                                  c_int, c_p]),
     'se3ds_nn_inpaint_workspace_bytes': (c_sz, [c_int, c_int, c_int]),

@@ -517,7 +517,7 @@ class GANManager(abc.ABC):
             f.write(_encode_png(pixels[example_idx]))
 
   def test(self, eval_examples=None, checkpoints=None, unit_test: bool = False, inception=None,
-           logger=None):
+           logger=None, frechet: str = 'host'):
     """The evaluation loop of the reference (:233-322) minus the polling task manager.  logger: a
     utils/logger.UniversalLogger; per checkpoint the row's values go to it as scalars and the nine
     image grids of the display batch's roll-out under the prefix test_split (:241,320-321).  eval_examples: parsed trajectory examples (what R2RVideoDataset.input_fn takes: a
@@ -529,7 +529,7 @@ class GANManager(abc.ABC):
     Per checkpoint: restore, roll the display batch out (_get_image_grid), write the EMA
     roll-out's frames as PNG, FID / RMSE per frame index for the generator and its EMA, one CSV
     row.  The step of a row (and of its image directory) is the number that ends the checkpoint's
-    name.  Returns the rows written."""
+    name.  frechet: EvalMetric's Frechet method, 'host' or 'device'.  Returns the rows written."""
     from se3ds_amd.datasets import indoor_datasets
     from se3ds_amd.utils import eval_metric
     if self.strategy.num_replicas_in_sync != 1:
@@ -552,7 +552,8 @@ class GANManager(abc.ABC):
                      else dataset.num_examples[self.test_split])
     metric = eval_metric.EvalMetric(ds=self.eval_ds, eval_num=self.eval_size or self.eval_num,
                                     batch_size=self.test_batch_size, strategy=None, avg_num=1,
-                                    eval_seq_len=self.eval_seq_len, inception=inception)
+                                    eval_seq_len=self.eval_seq_len, inception=inception,
+                                    frechet=frechet)
     if not hasattr(self, 'generator'):
       self._create_obj()
     rows = []

@@ -10,7 +10,8 @@ EvalMetric is the other half of the reference's evaluator (:66-343): the FID per
 roll-out against real frames, averaged over `avg_num` repeats, and the depth RMSE.  Real and
 generated frames go through the augment + crop + resize gather and Inception-v3 on the device
 (utils/inception_utils.py); their 2048-d pools are reduced there into binary64 moments
-(FeatureMoments), so only the mean and covariance reach the host for the Frechet distance."""
+(FeatureMoments), so only the mean and covariance reach the host for the Frechet distance -- or, with
+frechet='device', nothing but the distance does (inception_utils.frechet_distance_device)."""
 from typing import Callable, Dict, Iterator, List, NamedTuple, Optional
 
 import numpy as np
@@ -125,14 +126,19 @@ class EvalMetric:
   inception_utils.inception_model() (gin-configurable).  Augment draws come from a NumPy generator
   seeded with `seed`.  strategy: only None (a single device) is supported; per-rank
   FeatureMoments can be merged by the caller.  keep_pools: also keep the host copies of the pools
-  of the real set and of the last repeat (tests)."""
+  of the real set and of the last repeat (tests).  frechet: 'host' (NumPy / SciPy sqrtm, the
+  reference's formulation) or 'device' (FeatureMoments.fid(method='device'): the real set's matrix
+  square root is computed once per frame index and reused for every generator and repeat)."""
 
   def __init__(self, ds: Iterator, eval_num: int, batch_size: int, strategy=None, avg_num: int = 3,
                num_splits: int = 1, eval_seq_len: int = 5,
                inception: Optional[inception_utils.InceptionV3] = None, seed: int = 0,
-               keep_pools: bool = False) -> None:
+               keep_pools: bool = False, frechet: str = 'host') -> None:
     if strategy is not None:
       raise NotImplementedError('EvalMetric runs on one device; merge FeatureMoments across ranks')
+    if frechet not in inception_utils.FRECHET_METHODS:
+      raise ValueError(f'unknown Frechet method {frechet!r}: one of {inception_utils.FRECHET_METHODS}')
+    self.frechet = frechet
     self.ds = ds
     self.eval_num = eval_num
     self.batch_size = batch_size
@@ -201,7 +207,10 @@ class EvalMetric:
       rmse_total = {}
       gen = self._moments(frames_fn, 'generated_pools', rmse=rmse_total)
       for i in fid_list:
-        fid_list[i].append(gen[i].fid(self._real[i]))
+        if self.frechet == 'host':
+          fid_list[i].append(gen[i].fid(self._real[i]))
+        else:   # the real set owns the cached root; the trace term is symmetric in the two sets
+          fid_list[i].append(self._real[i].fid(gen[i], method=self.frechet))
         rmse_list[i].append(np.mean(rmse_total[i]))
     self.fid_list = fid_list
     fid = {k: np.mean(v) for k, v in fid_list.items()}

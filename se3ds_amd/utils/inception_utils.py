@@ -6,9 +6,11 @@ BN moving statistics).  Keras `conv2d_bn` is Conv2D without bias -> BatchNormali
 eps=1e-3) on its moving statistics -> ReLU; the batch norm is folded at load time into fp32 weights
 w * rsqrt(var + eps) per output channel with bias beta - mean * rsqrt(var + eps), so every layer is
 one se3ds_conv2d_fwd with its bias + ReLU epilogue.  Pooling, the input gather, the global average
-pool, the softmax and the binary64 feature moments are csrc/inception.hip.  The Frechet distance
-(sqrtm of a 2048 x 2048 matrix) and the Inception Score stay on the host in NumPy / SciPy, as in the
-reference.
+pool, the softmax and the binary64 feature moments are csrc/inception.hip.  The Frechet distance runs
+on the host in NumPy / SciPy as in the reference (sqrtm of a 2048 x 2048 product; the default), or,
+opt-in, on the device (csrc/frechet.hip, `frechet_distance_device`, `FeatureMoments.fid(method=
+'device')`): tr sqrt(S1 S2) = tr sqrt(R S2 R) with R = sqrt(S1), both roots of symmetric PSD matrices
+by a coupled Newton-Schulz iteration on a binary64 MFMA GEMM.  The Inception Score stays in NumPy.
 
 Weights: a `tf.train.Checkpoint(inception_v3=model)` directory (reference
 inception_utils.py:_inception_model_v3) read with utils/tf_bundle.py, or an .npz keyed by Keras layer
@@ -30,7 +32,7 @@ TensorFlow (not available to this project).  Every shape is checked at load.
 """
 import os
 import warnings
-from typing import Dict, List, Optional
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import numpy as np
 from scipy import linalg
@@ -577,6 +579,97 @@ def calculate_inception_score(pred, num_splits=10):
     scores.append(np.exp(kl_inception))
   return np.mean(scores), np.std(scores)
 
+# ------------------------------------------------------------------------------ device Frechet distance
+SQRT_CONVERGED, SQRT_CAP_REACHED, SQRT_NONFINITE = 0, 1, 2   # SE3DS_SQRT_* of include/se3ds_hip.h
+FRECHET_METHODS = ('host', 'device')
+
+
+class SqrtTrace(NamedTuple):
+  root: Optional[torch.Tensor]   # sqrt(A) on the device, or None
+  trace: float                   # tr sqrt(A)
+  iterations: int
+  status: int                    # SQRT_CONVERGED / SQRT_CAP_REACHED / SQRT_NONFINITE
+  norm: float                    # ||A||_F
+
+
+class FrechetResult(NamedTuple):
+  value: float
+  iterations: Tuple[int, int]    # of sqrt(sigma1) (0 when root1 was passed) and of sqrt(R sigma2 R)
+  converged: bool
+
+
+def _square_f64(name, *mats):
+  _lib.require_cuda(*mats)
+  n = mats[0].shape[-1]
+  for m in mats:
+    if m.dtype != torch.float64 or m.dim() != 2 or tuple(m.shape) != (n, n):
+      raise ValueError(f'{name}: expected binary64 ({n}, {n}) matrices, got {m.dtype} {tuple(m.shape)}')
+  return n
+
+
+def f64_gemm(a: torch.Tensor, b: torch.Tensor, alpha: float = 1.0, diag: float = 0.0,
+             out: Optional[torch.Tensor] = None) -> torch.Tensor:
+  """alpha * a @ b + diag * I of square binary64 device matrices (se3ds_f64_gemm)."""
+  n = _square_f64('f64_gemm', a, b)
+  a, b = a.contiguous(), b.contiguous()
+  if out is None:
+    out = torch.empty((n, n), dtype=torch.float64, device=a.device)
+  _chk(_L().se3ds_f64_gemm(a.data_ptr(), b.data_ptr(), out.data_ptr(), n, alpha, diag, _lib.stream()),
+       'se3ds_f64_gemm')
+  return out
+
+
+def _queue_sqrt_trace(a, max_iters, tol, root, result):
+  """Queues se3ds_sqrt_trace of `a` (contiguous); nothing is read back."""
+  n = a.shape[0]
+  nbytes = _L().se3ds_sqrt_trace_workspace_bytes(n)
+  ws = torch.empty(nbytes // 8, dtype=torch.float64, device=a.device)
+  _chk(_L().se3ds_sqrt_trace(a.data_ptr(), n, max_iters, tol, _lib.ptr(root), ws.data_ptr(), nbytes,
+                             result.data_ptr(), _lib.stream()), 'se3ds_sqrt_trace')
+
+
+def sqrt_trace_device(a: torch.Tensor, max_iters: int = 48, tol: float = 1e-10,
+                      want_root: bool = True) -> SqrtTrace:
+  """tr sqrt(a), and sqrt(a), of a symmetric PSD binary64 device matrix by the coupled Newton-Schulz
+  iteration (se3ds_sqrt_trace): the whole iteration is queued, then one 4-number block is read."""
+  n = _square_f64('sqrt_trace_device', a)
+  a = a.contiguous()
+  root = torch.empty((n, n), dtype=torch.float64, device=a.device) if want_root else None
+  result = torch.empty(4, dtype=torch.float64, device=a.device)
+  _queue_sqrt_trace(a, max_iters, tol, root, result)
+  r = result.cpu().tolist()
+  return SqrtTrace(root, r[0], int(r[1]), int(r[2]), r[3])
+
+
+def frechet_distance_device(mu1: torch.Tensor, sigma1: torch.Tensor, mu2: torch.Tensor,
+                            sigma2: torch.Tensor, root1: Optional[torch.Tensor] = None,
+                            max_iters: int = 48, tol: float = 1e-10) -> FrechetResult:
+  """|mu1 - mu2|^2 + tr S1 + tr S2 - 2 tr sqrt(R S2 R), R = sqrt(S1), of binary64 device statistics.
+  For symmetric PSD covariances tr sqrt(S1 S2) = tr sqrt(R S2 R), so both roots are of symmetric PSD
+  matrices.  root1 = sqrt(sigma1) is computed unless passed (FeatureMoments.sqrt_cov_device caches
+  it).  Everything is queued on the current stream; one block of 11 numbers is read at the end.
+  converged: both roots met the stop rule and the value is finite."""
+  _lib.require_cuda(mu1, mu2)
+  n = _square_f64('frechet_distance_device', sigma1, sigma2, *([] if root1 is None else [root1]))
+  for m in (mu1, mu2):
+    if m.dtype != torch.float64 or tuple(m.shape) != (n,):
+      raise ValueError(f'expected binary64 ({n},) means, got {m.dtype} {tuple(m.shape)}')
+  mu1, mu2, sigma1, sigma2 = (t.contiguous() for t in (mu1, mu2, sigma1, sigma2))
+  res = torch.zeros(12, dtype=torch.float64, device=sigma1.device)
+  if root1 is None:
+    root1 = torch.empty((n, n), dtype=torch.float64, device=sigma1.device)
+    _queue_sqrt_trace(sigma1, max_iters, tol, root1, res[0:4])
+  else:
+    root1 = root1.contiguous()
+  m = f64_gemm(f64_gemm(root1, sigma2), root1)
+  _queue_sqrt_trace(m, max_iters, tol, None, res[4:8])
+  _chk(_L().se3ds_frechet_terms(mu1.data_ptr(), mu2.data_ptr(), sigma1.data_ptr(), sigma2.data_ptr(), n,
+                                res[8:11].data_ptr(), _lib.stream()), 'se3ds_frechet_terms')
+  r = res.cpu().tolist()
+  value = r[8] + r[9] + r[10] - 2 * r[4]
+  ok = int(r[2]) == SQRT_CONVERGED and int(r[6]) == SQRT_CONVERGED and bool(np.isfinite(value))
+  return FrechetResult(value, (int(r[1]), int(r[5])), ok)
+
 
 class FeatureMoments:
   """Running count, sum and Gram matrix of (B, dim) fp32 feature rows, accumulated in binary64 on
@@ -589,9 +682,11 @@ class FeatureMoments:
     self._sum = torch.zeros(dim, dtype=torch.float64, device=self.device)
     self._gram = torch.zeros((dim, dim), dtype=torch.float64, device=self.device)
     self._extra = None   # merged host-side (count, sum, full gram)
+    self._root = None    # cached (mean, cov, sqrt(cov), iterations, status) on the device
 
   def update(self, pools: torch.Tensor):
     _lib.require_cuda(pools)
+    self._root = None
     if pools.dim() != 2 or pools.shape[1] != self.dim or pools.dtype != torch.float32:
       raise ValueError(f'expected fp32 (B, {self.dim}) rows, got {pools.dtype} {tuple(pools.shape)}')
     pools = pools.contiguous()
@@ -612,6 +707,7 @@ class FeatureMoments:
 
   def merge(self, other: 'FeatureMoments'):
     n, s, g = other.state()
+    self._root = None
     if self._extra is None:
       self._extra = (n, s, g)
     else:
@@ -637,7 +733,51 @@ class FeatureMoments:
   def cov(self):
     return self.mean_cov()[1]
 
-  def fid(self, other: 'FeatureMoments'):
+  def mean_cov_device(self):
+    """(mean (dim,), cov (dim, dim) full symmetric) as binary64 device tensors, the formula of
+    mean_cov() evaluated by se3ds_moments_mean_cov from the device moments: no download.  An
+    accumulator that merged host-side state uploads its merged state() first."""
+    if self.count < 2:
+      raise ValueError('a covariance needs at least two rows')
+    count, total, gram = self._count, self._sum, self._gram
+    if self._extra is not None:
+      n, s, g = self.state()
+      count = torch.tensor([n], dtype=torch.int64, device=self.device)
+      total, gram = torch.from_numpy(s).to(self.device), torch.from_numpy(g).to(self.device)
+    mean = torch.empty(self.dim, dtype=torch.float64, device=self.device)
+    cov = torch.empty((self.dim, self.dim), dtype=torch.float64, device=self.device)
+    _chk(_L().se3ds_moments_mean_cov(count.data_ptr(), total.data_ptr(), gram.data_ptr(), self.dim,
+                                     mean.data_ptr(), cov.data_ptr(), _lib.stream()),
+         'se3ds_moments_mean_cov')
+    return mean, cov
+
+  def _root_device(self, max_iters, tol):
+    if self._root is None or self._root[5:] != (max_iters, tol):
+      mean, cov = self.mean_cov_device()
+      r = sqrt_trace_device(cov, max_iters, tol)
+      self._root = (mean, cov, r.root, r.iterations, r.status, max_iters, tol)
+    return self._root
+
+  def sqrt_cov_device(self, max_iters: int = 48, tol: float = 1e-10) -> torch.Tensor:
+    """sqrt(cov) on the device (sqrt_trace_device), cached until the next update() / merge()."""
+    return self._root_device(max_iters, tol)[2]
+
+  def fid(self, other: 'FeatureMoments', method: str = 'host', max_iters: int = 48,
+          tol: float = 1e-10):
+    """The Frechet distance to `other`.  method='host': NumPy / SciPy on the downloaded moments
+    (the reference's sqrtm formulation).  method='device': frechet_distance_device with this
+    accumulator's cached root; if that does not converge or is not finite, a warning and the host
+    value."""
+    if method not in FRECHET_METHODS:
+      raise ValueError(f'unknown Frechet method {method!r}: one of {FRECHET_METHODS}')
+    if method == 'device':
+      mu1, sigma1, root1, _, status, _, _ = self._root_device(max_iters, tol)
+      mu2, sigma2 = other.mean_cov_device()
+      r = frechet_distance_device(mu1, sigma1, mu2, sigma2, root1=root1, max_iters=max_iters, tol=tol)
+      if r.converged and status == SQRT_CONVERGED:
+        return r.value
+      warnings.warn(f'device Frechet distance did not converge (root status {status}, iterations '
+                    f'{r.iterations}, value {r.value}); using the host path')
     mu1, sigma1 = self.mean_cov()
     mu2, sigma2 = other.mean_cov()
     return _calculate_frechet_distance(mu1, sigma1, mu2, sigma2)
