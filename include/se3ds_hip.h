@@ -804,6 +804,21 @@ size_t se3ds_crc32c_workspace_bytes(int64_t total_bytes, int n);
 int se3ds_crc32c_fields(void);
 int se3ds_crc32c_block_bytes(void);
 
+/* The zip / zlib CRC-32 (ISO 3309: reflected polynomial 0xEDB88320, init and final xor 0xffffffff;
+ * zlib.crc32) of n byte ranges of one device buffer in one call, each continued from a seed -- the
+ * checksum of the members of a checkpoint archive, whose .npy headers the host has already hashed
+ * (trainers/gan_manager.py save_checkpoint_async, utils/npz_writer.py).  The kernels, the schedule,
+ * the bounds and the BADSHAPE conditions are those of se3ds_crc32c_multi with the other polynomial.
+ * table_dev / host_table: int64 [n][se3ds_crc32z_fields() = 3] = byte offset into buf, length,
+ * seed (0 .. 2^32 - 1, anything else is BADSHAPE).  crc_dev[i] = zlib.crc32(range i, seed i): seed
+ * 0 is the plain CRC-32, an empty range gives its seed. */
+int se3ds_crc32z_multi(const uint8_t* buf, int64_t buf_bytes, const int64_t* table_dev,
+                       const int64_t* host_table, int n, uint32_t* crc_dev, void* workspace,
+                       size_t workspace_bytes, void* stream);
+size_t se3ds_crc32z_workspace_bytes(int64_t total_bytes, int n);
+int se3ds_crc32z_fields(void);
+int se3ds_crc32z_block_bytes(void);
+
 /* ======================================================================================
  * VLN perturbation augmentation -- inference/perturbation_utils.py:63-70.  csrc/perturb.hip.
  * ====================================================================================== */

@@ -67,6 +67,10 @@ _SIGS = {
     'se3ds_crc32c_workspace_bytes': (c_sz, [c_i64, c_int]),
     'se3ds_crc32c_fields': (c_int, []),
     'se3ds_crc32c_block_bytes': (c_int, []),
+    'se3ds_crc32z_multi': (c_int, [c_p, c_i64, c_p, c_p, c_int, c_p, c_p, c_sz, c_p]),
+    'se3ds_crc32z_workspace_bytes': (c_sz, [c_i64, c_int]),
+    'se3ds_crc32z_fields': (c_int, []),
+    'se3ds_crc32z_block_bytes': (c_int, []),
     'se3ds_collision_count': (c_int, [c_p, c_int, c_int, c_int, c_p, c_p, c_p, c_f, c_int, c_p, c_p]),
     'se3ds_collision_check_windows': (c_int, [c_p, c_p, c_int, c_int, c_int, c_int]),
     'se3ds_perspective_to_pointcloud': (c_int, [c_p, c_p, c_int, c_int, c_int, c_p, c_p, c_int, c_f, c_p, c_p,

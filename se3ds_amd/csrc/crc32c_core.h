@@ -20,6 +20,12 @@
 // consecutive blocks (acc = acc * x^(8 kBlockBytes) ^ raw), and multiplies by its lane constant; the
 // xor over the lanes times x^(8 kBlockBytes m) is the run's share of the segment's CRC.  Shares
 // combine by xor, which is exact and commutative: the result does not depend on their order.
+//
+// Two polynomials.  Everything that depends on P takes it as a template parameter whose default is
+// Castagnoli, so the CRC-32C callers read as before.  The zip / zlib CRC-32 (kPolyZip, reflected
+// 0xEDB88320) is the other instantiation; its table rows have a third field, a seed: the slice that
+// starts at the range's first byte starts from ~seed, which continues zlib.crc32(prefix) over the
+// range, and an empty range keeps its seed.
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -36,9 +42,11 @@ namespace se3ds {
 namespace crc32c {
 
 constexpr uint32_t kPoly = 0x82F63B78u;
+constexpr uint32_t kPolyZip = 0xEDB88320u;   // ISO 3309 / zlib / zip
 constexpr uint32_t kOne = 0x80000000u;   // x^0
 constexpr uint32_t kInit = 0xffffffffu;  // initial register and final xor
 constexpr int kFields = 2;               // int64 per table row: byte offset, length
+constexpr int kFieldsSeeded = 3;         // ... and the CRC of what precedes the range (0 .. 2^32 - 1)
 constexpr int kLanes = 64;
 constexpr int kSliceShift = 8;
 constexpr int kSliceBytes = 1 << kSliceShift;
@@ -47,23 +55,26 @@ constexpr int kBlockBytes = 1 << kBlockShift;   // the work-splitting granule
 constexpr int kTableWords = 4 * 256;            // slicing-by-4
 static_assert(kBlockBytes == kLanes * kSliceBytes, "a block is one slice per lane");
 
-SE3DS_HD constexpr uint32_t times_x(uint32_t a) { return (a >> 1) ^ (kPoly & (0u - (a & 1u))); }
+template <uint32_t kP = kPoly>
+SE3DS_HD constexpr uint32_t times_x(uint32_t a) { return (a >> 1) ^ (kP & (0u - (a & 1u))); }
 
 // a * b mod P, 32 steps
+template <uint32_t kP = kPoly>
 SE3DS_HD constexpr uint32_t gf_mul(uint32_t a, uint32_t b) {
   uint32_t p = 0;
   for (int i = 31; i >= 0; --i) {
     p ^= b & (0u - ((a >> i) & 1u));
-    b = times_x(b);
+    b = times_x<kP>(b);
   }
   return p;
 }
 
 // Word i of the slicing tables: table k = i >> 8 holds the register after byte i & 255 and k zero
 // bytes.  Table 0 is the byte table.
+template <uint32_t kP = kPoly>
 SE3DS_HD constexpr uint32_t table_entry(int i) {
   uint32_t c = (uint32_t)(i & 255);
-  for (int s = 8 * ((i >> 8) + 1); s > 0; --s) c = times_x(c);
+  for (int s = 8 * ((i >> 8) + 1); s > 0; --s) c = times_x<kP>(c);
   return c;
 }
 
@@ -71,24 +82,27 @@ SE3DS_HD constexpr uint32_t table_entry(int i) {
 struct Pow2 {
   uint32_t v[64];
 };
+template <uint32_t kP = kPoly>
 SE3DS_HD constexpr Pow2 make_pow2() {
   Pow2 t{};
   t.v[0] = kOne >> 8;
-  for (int k = 1; k < 64; ++k) t.v[k] = gf_mul(t.v[k - 1], t.v[k - 1]);
+  for (int k = 1; k < 64; ++k) t.v[k] = gf_mul<kP>(t.v[k - 1], t.v[k - 1]);
   return t;
 }
 
 // x^(8 n * 2^shift), n * 2^shift < 2^64: square-and-multiply over the set bits of n
+template <uint32_t kP = kPoly>
 SE3DS_HD uint32_t xpow8(uint64_t n, int shift, const Pow2& t) {
   uint32_t r = kOne;
   for (int k = shift; n != 0 && k < 64; ++k, n >>= 1)
-    if (n & 1u) r = r == kOne ? t.v[k] : gf_mul(r, t.v[k]);
+    if (n & 1u) r = r == kOne ? t.v[k] : gf_mul<kP>(r, t.v[k]);
   return r;
 }
 
 // what the partial of `lane` is multiplied by: the slices behind it in its block
+template <uint32_t kP = kPoly>
 SE3DS_HD uint32_t lane_multiplier(int lane, const Pow2& t) {
-  return xpow8((uint64_t)(kLanes - 1 - lane), kSliceShift, t);
+  return xpow8<kP>((uint64_t)(kLanes - 1 - lane), kSliceShift, t);
 }
 
 SE3DS_HD int64_t block_count(int64_t len) {
@@ -169,24 +183,27 @@ SE3DS_HD void slice_bounds(int64_t len, int64_t nb, int64_t c, int lane, int64_t
 }
 
 // One lane's share of blocks [c_lo, c_hi) of a segment, positioned at the end of block c_hi - 1.
+// init: the register in front of the segment's first byte.
+template <uint32_t kP = kPoly>
 SE3DS_HD uint32_t lane_partial(const uint8_t* seg, int64_t len, int64_t nb, int64_t c_lo, int64_t c_hi,
-                               int lane, uint32_t lane_mul, const uint32_t* t, const Pow2& pw) {
+                               int lane, uint32_t lane_mul, uint32_t init, const uint32_t* t, const Pow2& pw) {
   uint32_t acc = 0;
   for (int64_t c = c_lo; c < c_hi; ++c) {
     int64_t begin;
     uint32_t n;
     slice_bounds(len, nb, c, lane, &begin, &n);
-    if (c != c_lo) acc = gf_mul(acc, pw.v[kBlockShift]);
-    if (n != 0) acc ^= slice_crc(seg + begin, n, begin == 0 ? kInit : 0u, t);
+    if (c != c_lo) acc = gf_mul<kP>(acc, pw.v[kBlockShift]);
+    if (n != 0) acc ^= slice_crc(seg + begin, n, begin == 0 ? init : 0u, t);
   }
-  return gf_mul(acc, lane_mul);
+  return gf_mul<kP>(acc, lane_mul);
 }
 
 // Blocks [g0, g1) of the concatenated work of all segments.  prefix[s] = number of blocks in front
 // of segment s, prefix[n] = all.  Policy: xor_lanes(f) = xor of f(lane) over the lanes,
 // lane_multiplier(lane), emit(p, v): *p ^= v once.  The table is not trusted: a row that leaves
-// [0, buf_bytes) or disagrees with prefix is skipped.
-template <class Policy>
+// [0, buf_bytes) or disagrees with prefix is skipped.  kF = kFieldsSeeded: the row's third field
+// is its seed.
+template <class Policy, uint32_t kP = kPoly, int kF = kFields>
 SE3DS_HD void walk(const Policy& policy, const uint8_t* buf, int64_t buf_bytes, const int64_t* table,
                    const int64_t* prefix, int n, int64_t g0, int64_t g1, const uint32_t* t, const Pow2& pw,
                    uint32_t* crc) {
@@ -205,16 +222,17 @@ SE3DS_HD void walk(const Policy& policy, const uint8_t* buf, int64_t buf_bytes, 
       ++s;
       continue;
     }
-    const int64_t off = table[(int64_t)s * kFields], len = table[(int64_t)s * kFields + 1];
+    const int64_t off = table[(int64_t)s * kF], len = table[(int64_t)s * kF + 1];
     const int64_t nb = next - first;
     if (first <= g && off >= 0 && len > 0 && len <= buf_bytes && off <= buf_bytes - len &&
         block_count(len) == nb) {
       const int64_t c_lo = g - first, c_hi = g1 - first < nb ? g1 - first : nb;
       const uint8_t* seg = buf + off;
+      const uint32_t init = kF == kFieldsSeeded ? ~(uint32_t)table[(int64_t)s * kF + (kF - 1)] : kInit;
       uint32_t v = policy.xor_lanes([&](int lane) {
-        return lane_partial(seg, len, nb, c_lo, c_hi, lane, policy.lane_multiplier(lane), t, pw);
+        return lane_partial<kP>(seg, len, nb, c_lo, c_hi, lane, policy.lane_multiplier(lane), init, t, pw);
       });
-      if (nb != c_hi) v = gf_mul(v, xpow8((uint64_t)(nb - c_hi), kBlockShift, pw));
+      if (nb != c_hi) v = gf_mul<kP>(v, xpow8<kP>((uint64_t)(nb - c_hi), kBlockShift, pw));
       policy.emit(crc + s, v);
     }
     g = next < g1 ? next : g1;

@@ -345,15 +345,36 @@ class GANManager(abc.ABC):
         self.train_d(input_list[i])
       self.train_g_d(input_list[-1])
 
-  def train(self, train_ds=None, num_train_steps=None, logger=None, display_batch=None):
-    """Host loop of the reference (:387-423) minus the checkpoint files.  logger: a
-    utils/logger.UniversalLogger; the metrics go to it as scalars at every log_every_steps.  With a
-    display_batch as well (a trajectory batch, what _get_image_grid takes) the nine image grids of
-    its roll-out go out under the prefix 'train' where the reference saves a checkpoint and logs
-    them (:415-420).  Without a logger nothing is written."""
+  def train(self, train_ds=None, num_train_steps=None, logger=None, display_batch=None, checkpoints=None,
+            resume=False, max_to_keep=200, snapshot='device', staging_bytes=2 * (256 << 20)):
+    """Host loop of the reference (:387-423).  logger: a utils/logger.UniversalLogger; the metrics
+    go to it as scalars at every log_every_steps.  With a display_batch as well (a trajectory batch,
+    what _get_image_grid takes) the nine image grids of its roll-out go out under the prefix 'train'
+    where the reference saves a checkpoint and logs them (:415-420).  Without a logger nothing of
+    that is written.
+
+    checkpoints: None (the default: no file is written), 'sync' (save_checkpoint) or 'async'
+    (save_checkpoint_async with `snapshot` and `staging_bytes`).  model_dir/ckpt-<step>.npz is saved
+    where the reference calls ckpt_manager.save(step) -- step > num_batched_steps and
+    step % save_every_steps < num_batched_steps, before the image grids -- and
+    ckpt-<num_train_steps>.npz after the loop (:417,422); then the writer is waited for, and a
+    failure of it is raised.  After a file is in place the oldest ckpt-*.npz beyond max_to_keep
+    (the reference keeps 200, :348-349) are deleted.
+    resume: restore the highest-step ckpt-<step>.npz of model_dir, if any, before the first step
+    (:327-331); its path is left in self.restored_from (None: started from initialisation).
+    The global_step in a file is its value at the moment of the save, which the loop, like the
+    reference's, advances only afterwards: a resumed run repeats that loop index with the optimiser
+    iterations already advanced, as the reference does."""
+    if checkpoints not in (None, 'sync', 'async'):
+      raise ValueError(f"checkpoints: None, 'sync' or 'async', got {checkpoints!r}")
     self.global_batch_size = self.train_batch_size
     if not hasattr(self, 'generator'):
       self._create_obj()
+    if resume:
+      found = self._checkpoint_files()
+      self.restored_from = found[-1][1] if found else None
+      if found:
+        self.restore_checkpoint(self.restored_from)
     if train_ds is not None:
       self.train_ds = iter(train_ds)
     if self.train_ds is None:
@@ -367,12 +388,45 @@ class GANManager(abc.ABC):
         if logger is not None:
           logger.log_scalars(step, **result_dict)
         self._reset_metrics()
+      if checkpoints is not None and step > self.num_batched_steps and (
+          step % self.save_every_steps < self.num_batched_steps):
+        self._train_save(step, checkpoints, max_to_keep, snapshot, staging_bytes)
       if logger is not None and display_batch is not None and step > self.num_batched_steps and (
           step % self.save_every_steps < self.num_batched_steps):
         image_dict, _ = self._get_image_dict(self._get_image_grid(display_batch), display_batch,
                                              'train')
         logger.log_images(step, **image_dict)
       self.global_step += self.num_batched_steps
+    if checkpoints is not None:
+      self._train_save(num_train_steps, checkpoints, max_to_keep, snapshot, staging_bytes)
+      self.wait_for_checkpoint()
+
+  def _checkpoint_files(self):
+    """[(step, path)] of the ckpt-<step>.npz files of model_dir, in step order."""
+    found = []
+    for name in os.listdir(self.model_dir) if os.path.isdir(self.model_dir) else []:
+      m = re.fullmatch(r'ckpt-(\d+)\.npz', name)
+      if m:
+        found.append((int(m.group(1)), os.path.join(self.model_dir, name)))
+    return sorted(found)
+
+  def _prune_checkpoints(self, max_to_keep):
+    found = self._checkpoint_files()
+    for _, path in found[:max(len(found) - int(max_to_keep), 0)]:
+      os.remove(path)
+
+  def _writes_checkpoints(self):
+    """One replica, or rank 0 of the strategy's group: the replicas hold the same state."""
+    return self.strategy.num_replicas_in_sync == 1 or dist.get_rank(self.strategy.group) == 0
+
+  def _train_save(self, step, mode, max_to_keep, snapshot, staging_bytes):
+    path = os.path.join(self.model_dir, f'ckpt-{step}.npz')
+    if mode == 'async':
+      self.save_checkpoint_async(path, snapshot=snapshot, staging_bytes=staging_bytes,
+                                 after=lambda: self._prune_checkpoints(max_to_keep))
+    elif self._writes_checkpoints():
+      self.save_checkpoint(path)
+      self._prune_checkpoints(max_to_keep)
 
   def _reset_metrics(self):
     for key in self.metrics:
@@ -636,6 +690,35 @@ class GANManager(abc.ABC):
   def save_checkpoint(self, path):
     """One uncompressed .npz (reference: checkpoint_manager.save, :425-428)."""
     np.savez(path, **self.state_dict())
+
+  def save_checkpoint_async(self, path, snapshot='device', staging_bytes=2 * (256 << 20), writer_hook=None,
+                            after=None):
+    """The file of save_checkpoint -- the keys and arrays of state_dict() -- written off the step
+    (trainers/async_checkpoint.py): nothing goes through state_dict(), the members'
+    zip CRC-32s come from the device (se3ds_crc32z_multi) and one background thread writes the file
+    through utils/npz_writer from two pinned slabs of staging_bytes / 2.
+    snapshot='device': the training stream copies the ten arenas into one snapshot allocation
+    (created at the first save and kept; as large as the arenas) and goes on; the file holds the
+    state of this moment whatever the trainer does next.  snapshot='direct': no copy; the live
+    arenas are read and this call returns once the last device-to-host copy is queued, which the
+    training stream then waits for -- for a model whose snapshot does not fit.
+    Returns a handle: .done, .wait() (raises what the writer raised), .path.  A save requested while
+    one is in flight first waits for it and raises its failure.  Under DataParallelStrategy only
+    rank 0 of the group writes; the others get a finished handle.  writer_hook: a callable the
+    writer thread invokes before it consumes each slab; after: one it invokes once the file is in
+    place."""
+    from se3ds_amd.trainers import async_checkpoint
+    if not self._writes_checkpoints():
+      return async_checkpoint.CheckpointHandle(path)
+    if getattr(self, '_checkpointer', None) is None:
+      self._checkpointer = async_checkpoint.AsyncCheckpointer(self)
+    return self._checkpointer.save(path, snapshot=snapshot, staging_bytes=staging_bytes,
+                                   writer_hook=writer_hook, after=after)
+
+  def wait_for_checkpoint(self):
+    """Blocks until the save in flight, if any, is in place; raises what its writer raised."""
+    if getattr(self, '_checkpointer', None) is not None:
+      self._checkpointer.wait()
 
   def restore_checkpoint(self, path, strict=True):
     """Returns the keys of the file that matched nothing (reference: checkpoint.restore)."""
