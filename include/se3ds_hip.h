@@ -981,6 +981,42 @@ int se3ds_cmap_to_label(const void* image, int dtype, int64_t pixels, const int3
 int se3ds_label_to_color(const void* labels, int dtype, int64_t pixels, const int32_t* cmap, int k,
                          uint8_t* out, void* stream);
 
+/* ======================================================================================
+ * Point-cloud .ply bodies -- utils/ply.py, SE3DSModel.write_memory_as_pointcloud (reference
+ * models/models.py:154-178).  csrc/ply.hip, the characters in csrc/ply_format_core.h.
+ * ====================================================================================== */
+
+/* The ASCII body: per point the line `x y z r g b \n` (one space after every value), each float as
+ * Python's repr of the value widened to binary64 (shortest round-trip digits; positional when the
+ * decimal exponent of the first digit is in [-4, 16), else d[.ddd]e+XX; `nan`, `inf`, `-inf`, `-0.0`),
+ * each colour as a decimal integer.  coords: three fp32 rows of m values, row k at coords + k *
+ * row_stride (row_stride >= m: rows 0-2 of a (4, M) memory).  rgb: (m, 3) I32 or U8, dense.
+ * out: device bytes, any alignment, out_capacity >= m * se3ds_ply_max_line_bytes(); the lines are
+ * written back to back in input order from out[0], and nothing beyond that capacity is touched.
+ * out_bytes: device int64, receives the byte count.  workspace: device, 16-byte aligned,
+ * se3ds_ply_ascii_workspace_bytes(m) bytes (0: m is not valid).  0 <= m <= se3ds_ply_max_points() =
+ * 2^24; m = 0 launches nothing and writes nothing, out_bytes included.
+ * Three launches on `stream`, workgroups of se3ds_ply_chunk_points() points: records and chunk byte
+ * totals (phase bit 1), one workgroup scanning the totals into 64-bit offsets and out_bytes (2),
+ * characters through LDS with 16-byte stores (4).  phases: 7 is what callers pass; other non-empty
+ * subsets run those launches alone on a workspace the earlier ones filled (tools/ply_bench.py).
+ * Integers only, no atomics, no host synchronisation: the same input gives the same bytes.
+ * All checks run before the first HIP call.  BADDTYPE: rgb_dtype; BADSHAPE: m, row_stride, a null or
+ * misaligned pointer, out_capacity, phases outside 1..7; WORKSPACE: too small. */
+int se3ds_ply_ascii(const float* coords, int64_t row_stride, const void* rgb, int rgb_dtype,
+                    int64_t m, uint8_t* out, int64_t out_capacity, int64_t* out_bytes,
+                    void* workspace, size_t workspace_bytes, int phases, void* stream);
+size_t se3ds_ply_ascii_workspace_bytes(int64_t m);
+int se3ds_ply_chunk_points(void);
+int se3ds_ply_max_line_bytes(void);
+int64_t se3ds_ply_max_points(void);
+/* The binary_little_endian body: per point 15 bytes, float x, y, z then uchar red, green, blue, from
+ * the same inputs.  out: device, 16-byte aligned, out_capacity >= 15 * m.  flag: device int32 that the
+ * CALLER has zeroed; set to 1 when a colour lies outside [0, 255] (its low byte is written).  One
+ * launch; m = 0 launches nothing.  Checks and error codes as above. */
+int se3ds_ply_binary(const float* coords, int64_t row_stride, const void* rgb, int rgb_dtype,
+                     int64_t m, uint8_t* out, int64_t out_capacity, int32_t* flag, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

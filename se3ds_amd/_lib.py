@@ -107,6 +107,12 @@ _SIGS = {
     'se3ds_seq_finalize': (c_int, [c_p, c_p, c_int, c_int, c_int, c_p, c_p, c_p]),
     'se3ds_cmap_to_label': (c_int, [c_p, c_int, c_i64, c_p, c_int, c_p, c_p]),
     'se3ds_label_to_color': (c_int, [c_p, c_int, c_i64, c_p, c_int, c_p, c_p]),
+    'se3ds_ply_ascii': (c_int, [c_p, c_i64, c_p, c_int, c_i64, c_p, c_i64, c_p, c_p, c_sz, c_int, c_p]),
+    'se3ds_ply_ascii_workspace_bytes': (c_sz, [c_i64]),
+    'se3ds_ply_chunk_points': (c_int, []),
+    'se3ds_ply_max_line_bytes': (c_int, []),
+    'se3ds_ply_max_points': (c_i64, []),
+    'se3ds_ply_binary': (c_int, [c_p, c_i64, c_p, c_int, c_i64, c_p, c_i64, c_p, c_p]),
 }
 
 _lib = None

@@ -13,6 +13,7 @@ from se3ds_amd import _lib
 from se3ds_amd import constants
 from se3ds_amd.models import image_models
 from se3ds_amd.utils import pano_utils
+from se3ds_amd.utils import ply
 from se3ds_amd.utils import point_cloud_utils
 
 
@@ -143,20 +144,13 @@ class SE3DSModel(object):
   def set_memory_state(self, state: MemoryState):
     self._memory = self._clone_state(state)
 
-  def write_memory_as_pointcloud(self, filename):
-    """Writes memory at batch position 0 to an ASCII .ply file (reference :154-178)."""
+  def write_memory_as_pointcloud(self, filename, encoder='host', format='ascii'):
+    """Writes memory at batch position 0 to a .ply file (reference :154-178).  The default is the
+    reference's ASCII file from the host loop; encoder='device' formats the same bytes on the device,
+    format='binary_little_endian' (device only) writes 15-byte records (utils/ply.py)."""
     state = self.get_memory_state()
     point_cloud_utils.check_promise(state.rgb_coords.device)   # (a host synchronisation anyway)
-    xyz = state.rgb_coords[0, 0:3].cpu().numpy().T
-    rgb = state.rgb[0].cpu().numpy()
-    with open(filename, 'w') as fp:
-      fp.write('ply\nformat ascii 1.0 \n')
-      fp.write('element vertex %d\n' % xyz.shape[0])
-      fp.write('property float x\nproperty float y\nproperty float z\n')
-      fp.write('property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n')
-      for i in range(xyz.shape[0]):
-        fp.write('{} {} {} {} {} {} \n'.format(xyz[i, 0], xyz[i, 1], xyz[i, 2], rgb[i, 0],
-                                               rgb[i, 1], rgb[i, 2]))
+    ply.write_ply(filename, state.rgb_coords[0], state.rgb[0], format=format, encoder=encoder)
 
   def add_to_memory(self, pano_rgb, pano_semantic, pano_depth, position, mask_blurred=True):
     """Adds an equirectangular observation to the memory (reference :180-245)."""
