@@ -779,6 +779,70 @@ int se3ds_png_encode_max_row_bytes(void);
  * first part and `b` of its len_b further bytes -- how the second launch folds the strips' sums
  * (csrc/deflate_core.h adler_combine). */
 uint32_t se3ds_adler32_combine(uint32_t a, uint32_t b, int64_t len_b);
+/* se3ds_png_encode for the planes of a training record (datasets/record_writer.py), two of which --
+ * image/depth and proj/depth, datasets/indoor_datasets.py:193-204 -- are 16-bit grey.  Signature,
+ * table, strips, slots, the packing launch, sizes and Adler-32 are those of se3ds_png_encode, with
+ * one more value of field 3: 2 = one 16-bit sample per pixel, lying in host (little-endian) order in
+ * memory, row_bytes = 2 x width.  What is filtered and deflated is the big-endian byte sequence PNG
+ * stores (ISO/IEC 15948 7.1): file byte x of a row is memory byte x ^ 1, 2 bytes per pixel.  8-bit and
+ * 16-bit planes share the launch.  BADSHAPE etc. as se3ds_png_encode (a field 3 outside {1, 2, 3});
+ * the two size functions take this entry's tables. */
+int se3ds_png_encode_planes(const int64_t* table, const int64_t* host_table, int n,
+                            uint8_t* workspace, int64_t workspace_bytes, uint8_t* out,
+                            int64_t out_bytes, uint32_t* sizes_dev, int phases, void* stream);
+size_t se3ds_png_encode_planes_workspace_bytes(const int64_t* host_table, int n);
+int64_t se3ds_png_encode_planes_out_bytes(const int64_t* host_table, int n);
+
+/* ======================================================================================
+ * Writing training records -- the inverse of datasets/indoor_datasets.py:125-247.
+ * csrc/records.hip, datasets/record_writer.py.
+ * ====================================================================================== */
+
+/* The warp's fp32 results (models/models.py:273-293) -> the planes a record stores, one elementwise
+ * pass over `pixels` pixels.  Three independent pairs; a pair is skipped when both its pointers
+ * are null, and at least one must be given.
+ * proj_rgb: (pixels, 3) F32, void class -1 -> rgb_out uint8: truncated toward zero, saturated to
+ * [0, 255]; the void class, negatives and NaN are 0.
+ * proj_depth: (pixels) F32 in [0, 1] -> depth_out uint16 = floor((double)d * 65535 + 0.5) saturated
+ * to [0, 65535], NaN -> 0: the inverse of the decoder's u16 / 65535 for all 65 536 codes.  Also for
+ * a float target depth (image/depth).
+ * proj_mask: (pixels) F32 -> mask_out uint8: 255 where the mask is 1, otherwise 0.
+ * Where all pointers are 16-byte aligned a thread takes four pixels per load; otherwise one.
+ * BADSHAPE: pixels < 1, half a pair, no pair, a float pointer off 4 bytes, depth_out off 2. */
+int se3ds_record_planes(const float* proj_rgb, const float* proj_depth, const float* proj_mask,
+                        int64_t pixels, uint8_t* rgb_out, uint16_t* depth_out, uint8_t* mask_out,
+                        void* stream);
+
+/* Copies n byte ranges from m source buffers to their offsets in `out` in one launch -- how a
+ * record file is put together from the literals the host made (PNG signature, IHDR, IEND, the IDAT
+ * framing, protobuf keys and varints, record lengths) and the encoder's compact streams.
+ * sources_host: HOST int64 [m][2] = device pointer, bytes; m <= 8.  table_dev / host_table: int64
+ * [n][se3ds_assemble_fields() = 4] = source index, source offset, destination offset, length.
+ * Offsets and lengths need no alignment.  One workgroup per segment: the caller splits a longer
+ * range into segments of at most se3ds_assemble_max_segment_bytes().  The kernel stores 16 bytes at
+ * a time only at 16-byte-aligned destinations and single bytes at a segment's edges; it reads the
+ * source as aligned words (shifted together) or single bytes, and never outside a segment's range.
+ * Bytes of out outside the destinations are not written.
+ * host_table is validated before anything runs (BADSHAPE: n < 1 or > 2^24, m outside 1..8, a null pointer, a
+ * source index outside [0, m), a length outside [0, max segment], a range that leaves its source,
+ * a destination that leaves [0, out_bytes) or starts before the end of the one in front:
+ * destinations ascend and are disjoint).  One launch on `stream`, no atomics. */
+int se3ds_assemble_segments(const int64_t* sources_host, int m, const int64_t* table_dev,
+                            const int64_t* host_table, int n, uint8_t* out, int64_t out_bytes,
+                            void* stream);
+int se3ds_assemble_fields(void);
+int64_t se3ds_assemble_max_segment_bytes(void);
+
+/* Writes device-resident CRC words (the results of se3ds_crc32z_multi / se3ds_crc32c_multi) into
+ * `out` without a round trip through the host.  table_dev / host_table: int64
+ * [n][se3ds_patch_crc_fields() = 3] = index into crc_dev, byte offset in out, form.  Form 0: the raw
+ * value big-endian (a PNG chunk's CRC); form 1: TFRecord's masked CRC-32C,
+ * ((c >> 15 | c << 17) + 0xa282ead8) little-endian.  Offsets need no alignment.
+ * BADSHAPE: n < 1 or > 2^24, a null pointer, an index outside [0, crc_count), a form outside {0, 1}, an
+ * offset outside [0, out_bytes - 4] or before the end of the patch in front. */
+int se3ds_patch_crc(const uint32_t* crc_dev, int crc_count, const int64_t* table_dev,
+                    const int64_t* host_table, int n, uint8_t* out, int64_t out_bytes, void* stream);
+int se3ds_patch_crc_fields(void);
 
 /* CRC-32C (Castagnoli: reflected polynomial 0x82F63B78, init and final xor 0xffffffff; RFC 3720
  * B.4, utils/tf_bundle.crc32c) of n byte ranges of one device buffer in one call -- the checksum of

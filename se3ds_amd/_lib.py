@@ -63,6 +63,15 @@ _SIGS = {
     'se3ds_png_encode_fields': (c_int, []),
     'se3ds_png_encode_max_row_bytes': (c_int, []),
     'se3ds_adler32_combine': (ctypes.c_uint32, [ctypes.c_uint32, ctypes.c_uint32, c_i64]),
+    'se3ds_png_encode_planes': (c_int, [c_p, c_p, c_int, c_p, c_i64, c_p, c_i64, c_p, c_int, c_p]),
+    'se3ds_png_encode_planes_workspace_bytes': (c_sz, [c_p, c_int]),
+    'se3ds_png_encode_planes_out_bytes': (c_i64, [c_p, c_int]),
+    'se3ds_record_planes': (c_int, [c_p, c_p, c_p, c_i64, c_p, c_p, c_p, c_p]),
+    'se3ds_assemble_segments': (c_int, [c_p, c_int, c_p, c_p, c_int, c_p, c_i64, c_p]),
+    'se3ds_assemble_fields': (c_int, []),
+    'se3ds_assemble_max_segment_bytes': (c_i64, []),
+    'se3ds_patch_crc': (c_int, [c_p, c_int, c_p, c_p, c_int, c_p, c_i64, c_p]),
+    'se3ds_patch_crc_fields': (c_int, []),
     'se3ds_crc32c_multi': (c_int, [c_p, c_i64, c_p, c_p, c_int, c_p, c_p, c_sz, c_p]),
     'se3ds_crc32c_workspace_bytes': (c_sz, [c_i64, c_int]),
     'se3ds_crc32c_fields': (c_int, []),

@@ -101,8 +101,12 @@ class Encoder {
   // s_.data, rows x (1 + row_bytes) <= kMaxStripBytes bytes.  mode 0..4: that filter type on every
   // row; kFilterAdaptive: per row the type with the smallest sum of |int8(residual)|, ties to the
   // lowest type.  The row above row0 is read from the image.  Returns the byte count.
+  // swap16: the image holds 16-bit samples in host (little-endian) order and bpp is 2; what is
+  // filtered is the big-endian byte sequence PNG stores: file byte x of a row is memory byte x ^ 1
+  // (row_bytes is even, so x ^ 1 stays inside the row).
   SE3DS_HD uint32_t filter(const uint8_t* image, uint32_t row_bytes, uint32_t bpp, uint32_t mode,
-                           uint32_t row0, uint32_t rows) {
+                           uint32_t row0, uint32_t rows, bool swap16 = false) {
+    const uint32_t flip = swap16 ? 1u : 0u;
     const uint32_t lane = (uint32_t)p_.lane();
     const uint32_t pitch = 1u + row_bytes;
     p_.sync();   // the lanes are done with the previous strip
@@ -114,7 +118,7 @@ class Encoder {
         uint32_t sum[5] = {0, 0, 0, 0, 0};
         for (uint32_t x = lane; x < row_bytes; x += Policy::kLanes) {
           uint32_t res[5];
-          residuals(cur, up, x, bpp, res);
+          residuals(cur, up, x, bpp, flip, res);
           for (int t = 0; t < 5; ++t) sum[t] += cost(res[t]);   // < 2^32: 65534 x 128
         }
         type = 0;
@@ -131,7 +135,7 @@ class Encoder {
       if (lane == 0) dst[0] = (uint8_t)type;
       for (uint32_t x = lane; x < row_bytes; x += Policy::kLanes) {
         uint32_t res[5];
-        residuals(cur, up, x, bpp, res);
+        residuals(cur, up, x, bpp, flip, res);
         dst[1 + x] = (uint8_t)res[type];
       }
     }
@@ -190,13 +194,14 @@ class Encoder {
 
  private:
   // the five residuals of byte x of a row: a = the byte one pixel to the left, b = the byte above,
-  // c = the byte above-left, all 0 outside the image
+  // c = the byte above-left, all 0 outside the image.  x counts file bytes; flip (0 or 1) is xor-ed
+  // into every memory index (filter(): swap16)
   SE3DS_HD static void residuals(const uint8_t* cur, const uint8_t* up, uint32_t x, uint32_t bpp,
-                                 uint32_t (&res)[5]) {
-    const uint32_t v = cur[x];
-    const uint32_t a = x >= bpp ? cur[x - bpp] : 0u;
-    const uint32_t b = up ? up[x] : 0u;
-    const uint32_t c = (up && x >= bpp) ? up[x - bpp] : 0u;
+                                 uint32_t flip, uint32_t (&res)[5]) {
+    const uint32_t v = cur[x ^ flip];
+    const uint32_t a = x >= bpp ? cur[(x - bpp) ^ flip] : 0u;
+    const uint32_t b = up ? up[x ^ flip] : 0u;
+    const uint32_t c = (up && x >= bpp) ? up[(x - bpp) ^ flip] : 0u;
     res[0] = v;
     res[1] = (v - a) & 0xffu;
     res[2] = (v - b) & 0xffu;

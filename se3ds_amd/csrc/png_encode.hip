@@ -4,6 +4,8 @@
 // uint8 sheet (tf.cast(x * 255.0, tf.uint8) + images_to_grid, utils/image_grid.py:24-51), and
 // se3ds_png_encode turns many uint8 images into zlib streams -- filtering and deflate.  The encoder
 // is deflate_core.h; this file is its 64-lane policy, the two kernels and the entry points.
+// se3ds_png_encode_planes is the same pair of launches for the planes of a training record
+// (datasets/record_writer.py), whose table may also name 16-bit grey planes (field 3 = 2).
 //
 // Schedule: an image is cut into strips of max(1, 65535 / (1 + row_bytes)) rows; one wavefront (one
 // 64-thread workgroup) per strip, grid = the strips of all images.  A strip reads the row above its
@@ -86,8 +88,9 @@ png_encode_kernel(const int64_t* __restrict__ table, int n, int64_t total_strips
   uint8_t* slot = workspace + meta_bytes(total_strips) + d[7] + k * g.slot_bytes;
   const WavePolicy policy;
   deflate::Encoder<WavePolicy> encoder(policy, shared, slot);
+  // field 3 = 2 (se3ds_png_encode_planes only): 16-bit samples in host order
   const uint32_t bytes = encoder.filter(image, (uint32_t)row_bytes, (uint32_t)d[3], (uint32_t)d[4],
-                                        (uint32_t)row0, (uint32_t)rows);
+                                        (uint32_t)row0, (uint32_t)rows, d[3] == 2);
   const uint32_t length = encoder.compress(bytes, k == g.strips - 1);
   if (threadIdx.x == 0) {
     uint32_t* meta = reinterpret_cast<uint32_t*>(workspace) + strip * kMetaWords;
@@ -152,16 +155,17 @@ grid_quantize_kernel(const T* __restrict__ src, int h, int w, int c, int nx, int
 }
 
 // The host copy of the table: every row's own fields, and the cumulative ones against what this
-// file derives.  Fills the totals.
-int check_table(const int64_t* host_table, int n, int64_t* total_strips, int64_t* slots_bytes,
-                int64_t* out_bytes) {
+// file derives.  Fills the totals.  planes: the table of se3ds_png_encode_planes, whose field 3 may
+// also be 2.
+int check_table(const int64_t* host_table, int n, bool planes, int64_t* total_strips,
+                int64_t* slots_bytes, int64_t* out_bytes) {
   if (n < 1 || n > 65535 || !host_table) return SE3DS_E_BADSHAPE;
   int64_t strips = 0, slots = 0, outs = 0;
   for (int i = 0; i < n; ++i) {
     const int64_t* d = host_table + (int64_t)i * kEncodeFields;
     const int64_t height = d[1], row_bytes = d[2], bpp = d[3], mode = d[4];
     if (d[0] == 0 || height < 1 || height > INT32_MAX / 2 || row_bytes < 1) return SE3DS_E_BADSHAPE;
-    if ((bpp != 1 && bpp != 3) || row_bytes % bpp != 0) return SE3DS_E_BADSHAPE;
+    if ((bpp != 1 && bpp != 3 && !(planes && bpp == 2)) || row_bytes % bpp != 0) return SE3DS_E_BADSHAPE;
     if (row_bytes > kEncodeMaxRowBytes) return SE3DS_E_UNSUPPORTED;
     if (mode < 0 || mode > (int64_t)deflate::kFilterAdaptive) return SE3DS_E_BADSHAPE;
     const Geometry g = geometry(height, row_bytes);
@@ -195,23 +199,23 @@ extern "C" uint32_t se3ds_adler32_combine(uint32_t a, uint32_t b, int64_t len_b)
 
 extern "C" size_t se3ds_png_encode_workspace_bytes(const int64_t* host_table, int n) {
   int64_t strips = 0, slots = 0, outs = 0;
-  if (check_table(host_table, n, &strips, &slots, &outs) != SE3DS_OK) return 0;
+  if (check_table(host_table, n, false, &strips, &slots, &outs) != SE3DS_OK) return 0;
   return (size_t)(meta_bytes(strips) + slots);
 }
 
 extern "C" int64_t se3ds_png_encode_out_bytes(const int64_t* host_table, int n) {
   int64_t strips = 0, slots = 0, outs = 0;
-  if (check_table(host_table, n, &strips, &slots, &outs) != SE3DS_OK) return 0;
+  if (check_table(host_table, n, false, &strips, &slots, &outs) != SE3DS_OK) return 0;
   return outs;
 }
 
-extern "C" int se3ds_png_encode(const int64_t* table, const int64_t* host_table, int n,
-                                uint8_t* workspace, int64_t workspace_bytes, uint8_t* out,
-                                int64_t out_bytes, uint32_t* sizes_dev, int phases, void* stream) {
+static int encode(const int64_t* table, const int64_t* host_table, int n, bool planes,
+                  uint8_t* workspace, int64_t workspace_bytes, uint8_t* out, int64_t out_bytes,
+                  uint32_t* sizes_dev, int phases, void* stream) {
   if (!table || !workspace || !out || !sizes_dev || phases < 1 || phases > 3) return SE3DS_E_BADSHAPE;
   if ((reinterpret_cast<uintptr_t>(workspace) & 15u) != 0) return SE3DS_E_BADSHAPE;
   int64_t strips = 0, slots = 0, outs = 0;
-  const int rc = check_table(host_table, n, &strips, &slots, &outs);
+  const int rc = check_table(host_table, n, planes, &strips, &slots, &outs);
   if (rc != SE3DS_OK) return rc;
   if (workspace_bytes < meta_bytes(strips) + slots) return SE3DS_E_WORKSPACE;
   if (out_bytes < outs) return SE3DS_E_BADSHAPE;
@@ -225,6 +229,33 @@ extern "C" int se3ds_png_encode(const int64_t* table, const int64_t* host_table,
   hipLaunchKernelGGL(png_compact_kernel, dim3((unsigned)strips), dim3(kCompactThreads), 0,
                      as_stream(stream), table, n, strips, workspace, out, sizes_dev);
   return check_launch("png_compact");
+}
+
+extern "C" int se3ds_png_encode(const int64_t* table, const int64_t* host_table, int n,
+                                uint8_t* workspace, int64_t workspace_bytes, uint8_t* out,
+                                int64_t out_bytes, uint32_t* sizes_dev, int phases, void* stream) {
+  return encode(table, host_table, n, false, workspace, workspace_bytes, out, out_bytes, sizes_dev,
+                phases, stream);
+}
+
+extern "C" size_t se3ds_png_encode_planes_workspace_bytes(const int64_t* host_table, int n) {
+  int64_t strips = 0, slots = 0, outs = 0;
+  if (check_table(host_table, n, true, &strips, &slots, &outs) != SE3DS_OK) return 0;
+  return (size_t)(meta_bytes(strips) + slots);
+}
+
+extern "C" int64_t se3ds_png_encode_planes_out_bytes(const int64_t* host_table, int n) {
+  int64_t strips = 0, slots = 0, outs = 0;
+  if (check_table(host_table, n, true, &strips, &slots, &outs) != SE3DS_OK) return 0;
+  return outs;
+}
+
+extern "C" int se3ds_png_encode_planes(const int64_t* table, const int64_t* host_table, int n,
+                                       uint8_t* workspace, int64_t workspace_bytes, uint8_t* out,
+                                       int64_t out_bytes, uint32_t* sizes_dev, int phases,
+                                       void* stream) {
+  return encode(table, host_table, n, true, workspace, workspace_bytes, out, out_bytes, sizes_dev,
+                phases, stream);
 }
 
 extern "C" int se3ds_grid_quantize(const void* src, int dtype, int n, int h, int w, int c, int ny,

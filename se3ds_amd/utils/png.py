@@ -400,9 +400,13 @@ def _chunk(tag: bytes, data: bytes) -> bytes:
   return struct.pack('>I', len(data)) + tag + data + struct.pack('>I', zlib.crc32(tag + data))
 
 
-def png_container(height: int, width: int, channels: int, zlib_stream: bytes) -> bytes:
-  """Signature, IHDR (8-bit grey or RGB, non-interlaced), one IDAT chunk, IEND."""
-  ihdr = struct.pack('>IIBBBBB', width, height, 8, 0 if channels == 1 else 2, 0, 0, 0)
+def png_container(height: int, width: int, channels: int, zlib_stream: bytes, bit_depth: int = 8
+                  ) -> bytes:
+  """Signature, IHDR (8-bit grey or RGB, or 16-bit grey with bit_depth=16; non-interlaced), one IDAT
+  chunk, IEND."""
+  if bit_depth not in (8, 16) or (bit_depth == 16 and channels != 1):
+    raise ValueError(f'png_container: {channels} channel(s) at bit depth {bit_depth}')
+  ihdr = struct.pack('>IIBBBBB', width, height, bit_depth, 0 if channels == 1 else 2, 0, 0, 0)
   return SIGNATURE + _chunk(b'IHDR', ihdr) + _chunk(b'IDAT', zlib_stream) + _chunk(b'IEND', b'')
 
 
@@ -427,10 +431,31 @@ def encode_table(pointers: Sequence[int], geometries: Sequence[Tuple[int, int, i
   return table
 
 
+_SAMPLES_16 = tuple(t for t in (torch.int16, getattr(torch, 'uint16', None), np.dtype(np.uint16))
+                    if t is not None)
+
+
+def _is_16bit(dtype) -> bool:
+  return dtype in _SAMPLES_16
+
+
 def _check_pixels(shape, dtype, what):
-  if dtype not in (torch.uint8, np.dtype(np.uint8)) or len(shape) != 3 or shape[2] not in (1, 3) or \
-      shape[0] < 1 or shape[1] < 1:
-    raise ValueError(f'{what}: uint8 (H,W,1) or (H,W,3) expected, got {dtype} {tuple(shape)}')
+  ok = len(shape) == 3 and shape[0] >= 1 and shape[1] >= 1
+  if ok and _is_16bit(dtype):
+    ok = shape[2] == 1
+  elif ok:
+    ok = dtype in (torch.uint8, np.dtype(np.uint8)) and shape[2] in (1, 3)
+  if not ok:
+    raise ValueError(f'{what}: uint8 (H,W,1) or (H,W,3), or 16-bit (H,W,1), expected, got {dtype} '
+                     f'{tuple(shape)}')
+
+
+def plane_geometry(x) -> Tuple[int, int, int]:
+  """(height, row_bytes, field 3 of the encoder's table) of an (H,W,C) image: bytes per pixel 1 or
+  3 for uint8, 2 for a 16-bit grey plane (se3ds_png_encode_planes)."""
+  if _is_16bit(x.dtype):
+    return int(x.shape[0]), 2 * int(x.shape[1]), 2
+  return int(x.shape[0]), int(x.shape[1]) * int(x.shape[2]), int(x.shape[2])
 
 
 def encode_streams(images: Sequence[torch.Tensor], filters='adaptive', fill: int = None
@@ -438,7 +463,10 @@ def encode_streams(images: Sequence[torch.Tensor], filters='adaptive', fill: int
   """The device half of encode_png_batch: -> (table, sizes, streams).  table: the descriptor table
   (encode_table); sizes: uint32 (n, 2) = bytes of each image's deflate stream, Adler-32 of its
   filtered bytes; streams: the downloaded compact buffer, image i's stream at table[i, 6].  fill:
-  the output buffer is set to this byte before the launches (tests look at what stays untouched)."""
+  the output buffer is set to this byte before the launches (tests look at what stays untouched).
+  A 16-bit plane -- (H,W,1) torch.int16 holding the bit patterns of uint16, the convention of
+  datasets.indoor_datasets.RAW_DTYPES, or torch.uint16 -- has 2 in field 3 of its row and sends the
+  whole batch through se3ds_png_encode_planes; a batch of uint8 images takes se3ds_png_encode."""
   images = list(images)
   _lib.require_cuda(*images)
   dev = images[0].device
@@ -450,11 +478,12 @@ def encode_streams(images: Sequence[torch.Tensor], filters='adaptive', fill: int
   modes = _filter_modes(filters, len(images))
   L = _lib.lib()
   n = len(images)
-  geometries = [(x.shape[0], x.shape[1] * x.shape[2], x.shape[2]) for x in images]
+  geometries = [plane_geometry(x) for x in images]
   table = encode_table([x.data_ptr() for x in images], geometries, modes)
   assert table.shape[1] == L.se3ds_png_encode_fields()
-  workspace_bytes = L.se3ds_png_encode_workspace_bytes(table.ctypes.data, n)
-  out_bytes = L.se3ds_png_encode_out_bytes(table.ctypes.data, n)
+  entry = 'se3ds_png_encode_planes' if any(g[2] == 2 for g in geometries) else 'se3ds_png_encode'
+  workspace_bytes = getattr(L, entry + '_workspace_bytes')(table.ctypes.data, n)
+  out_bytes = getattr(L, entry + '_out_bytes')(table.ctypes.data, n)
   head = (8 * n + 15) & ~15   # the sizes lead the download buffer
   with torch.cuda.device(dev):
     staging = torch.from_numpy(table.reshape(-1)).pin_memory()
@@ -463,10 +492,10 @@ def encode_streams(images: Sequence[torch.Tensor], filters='adaptive', fill: int
     result = torch.empty((head + out_bytes,), dtype=torch.uint8, device=dev)
     if fill is not None:
       result.fill_(fill)
-    rc = L.se3ds_png_encode(_lib.ptr(table_dev), table.ctypes.data, n, _lib.ptr(workspace),
-                            workspace_bytes, _lib.ptr(result) + head, out_bytes, _lib.ptr(result), 3,
-                            _lib.stream())
-    _lib.check(rc, 'se3ds_png_encode')
+    rc = getattr(L, entry)(_lib.ptr(table_dev), table.ctypes.data, n, _lib.ptr(workspace),
+                           workspace_bytes, _lib.ptr(result) + head, out_bytes, _lib.ptr(result), 3,
+                           _lib.stream())
+    _lib.check(rc, entry)
     host = torch.empty((head + out_bytes,), dtype=torch.uint8, pin_memory=True)
     host.copy_(result, non_blocking=True)
     torch.cuda.current_stream().synchronize()
@@ -475,7 +504,8 @@ def encode_streams(images: Sequence[torch.Tensor], filters='adaptive', fill: int
 
 
 def encode_png_batch(images: Sequence[torch.Tensor], filters='adaptive', device=None) -> List[bytes]:
-  """uint8 device tensors (H,W,1|3), any mix of sizes -> their PNG files, encoded on the device:
+  """uint8 device tensors (H,W,1|3) and 16-bit grey ones (H,W,1) (torch.int16 bit patterns of
+  uint16, or torch.uint16), any mix of sizes -> their PNG files, encoded on the device:
   one upload (the descriptor table), se3ds_png_encode's two launches (csrc/png_encode.hip: filter
   and deflate every strip of every image, one wavefront each; pack the strips), one download (the
   sizes and the packed streams).  The host adds what has no width: signature, IHDR, the zlib
@@ -497,7 +527,8 @@ def encode_png_batch(images: Sequence[torch.Tensor], filters='adaptive', device=
   for row, (size, adler) in zip(table, sizes):
     at, h, rb, bpp = int(row[6]), int(row[1]), int(row[2]), int(row[3])
     stream = b'\x78\x01' + streams[at:at + int(size)].tobytes() + struct.pack('>I', int(adler))
-    files.append(png_container(h, rb // bpp, bpp, stream))
+    files.append(png_container(h, rb // bpp, 1, stream, 16) if bpp == 2 else
+                 png_container(h, rb // bpp, bpp, stream))
   return files
 
 
@@ -508,7 +539,11 @@ def _paeth_predictor(a, b, c):
 
 
 def filter_rows_host(pixels: np.ndarray, mode: int) -> np.ndarray:
-  """uint8 (H,W,C) -> the filtered scan lines uint8 (H, 1 + W*C) under the device encoder's rule."""
+  """uint8 (H,W,C) -> the filtered scan lines uint8 (H, 1 + W*C) under the device encoder's rule.
+  uint16 (H,W,1): the same rule on the big-endian bytes PNG stores, 2 bytes per pixel -> (H, 1 + 2W)."""
+  if pixels.dtype == np.uint16:
+    pixels = np.ascontiguousarray(pixels.astype('>u2')).view(np.uint8).reshape(
+        pixels.shape[0], pixels.shape[1], 2)
   h, w, c = pixels.shape
   cur = pixels.reshape(h, w * c).astype(np.int32)
   left = np.zeros_like(cur)
@@ -532,10 +567,11 @@ def filter_rows_host(pixels: np.ndarray, mode: int) -> np.ndarray:
 def encode_png_host(pixels: np.ndarray, filters='adaptive') -> bytes:
   """The CPU encoder: the same filters in NumPy, then zlib with Z_RLE (distance-1 matches only,
   as the device encoder).  The file decodes to the same pixels as encode_png_batch's; its bytes
-  need not be equal."""
+  need not be equal.  A uint16 (H,W,1) array becomes a 16-bit greyscale file."""
   pixels = np.ascontiguousarray(pixels)
   _check_pixels(pixels.shape, pixels.dtype, 'encode_png_host')
   filtered = filter_rows_host(pixels, _filter_mode(filters))
   z = zlib.compressobj(6, zlib.DEFLATED, 15, 9, zlib.Z_RLE)
   h, w, c = pixels.shape
-  return png_container(h, w, c, z.compress(filtered.tobytes()) + z.flush())
+  return png_container(h, w, c, z.compress(filtered.tobytes()) + z.flush(),
+                       16 if pixels.dtype == np.uint16 else 8)

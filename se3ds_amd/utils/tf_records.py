@@ -144,11 +144,54 @@ def frame_record(rec: bytes) -> bytes:
           struct.pack('<I', mask_crc(crc32c(rec))))
 
 
-def write_records(path: str, records: Iterable[bytes]):
-  """The inverse of read_records."""
-  with open(path, 'wb') as f:
-    for rec in records:
-      f.write(frame_record(rec))
+def frame_with_crcs(rec: bytes, length_crc: int, payload_crc: int) -> bytes:
+  """frame_record from the raw (unmasked) CRC-32C of the 8 length bytes and of the payload."""
+  return (struct.pack('<QI', len(rec), mask_crc(int(length_crc))) + bytes(rec) +
+          struct.pack('<I', mask_crc(int(payload_crc))))
+
+
+def write_records(path: str, records: Iterable[bytes], checksums: str = 'host',
+                  slab_bytes: int = 256 << 20, device=None):
+  """The inverse of read_records.  checksums='host' (the default): the Python byte loop of
+  `frame_record`.  checksums='device': both CRC-32C of every record come from the device
+  (`utils.crc32c.crc32c_host_slabs`), for payloads that are made on the host -- an evaluation
+  trajectory of `datasets.record_writer.encode_trajectory_example` is some 100 MB; records are
+  gathered until `slab_bytes` are pending, then checked in one go and written.  The bytes of the
+  file are the same either way.  The file is written as `<path>.tmp` and renamed at the end; on an
+  error the temporary file is removed and nothing is left under `path`."""
+  if checksums not in ('host', 'device'):
+    raise ValueError(f"checksums: 'host' or 'device', got {checksums!r}")
+  tmp = path + '.tmp'
+  f = open(tmp, 'wb')
+  try:
+    if checksums == 'host':
+      for rec in records:
+        f.write(frame_record(rec))
+    else:
+      from se3ds_amd.utils import crc32c as crc32c_dev
+
+      def flush(pending):
+        items = [x for rec in pending for x in (struct.pack('<Q', len(rec)), rec)]
+        crcs = crc32c_dev.crc32c_host_slabs(items, slab_bytes=slab_bytes, device=device)
+        for i, rec in enumerate(pending):
+          f.write(frame_with_crcs(rec, crcs[2 * i], crcs[2 * i + 1]))
+
+      pending, held = [], 0
+      for rec in records:
+        pending.append(bytes(rec))
+        held += len(pending[-1]) + 8
+        if held >= slab_bytes:
+          flush(pending)
+          pending, held = [], 0
+      if pending:
+        flush(pending)
+    f.close()
+    os.replace(tmp, path)
+  except BaseException:
+    f.close()
+    if os.path.exists(tmp):
+      os.remove(tmp)
+    raise
 
 
 # ------------------------------------------------------------------------------- Example

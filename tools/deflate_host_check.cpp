@@ -9,6 +9,8 @@
 //   kind 0, one strip of filtered bytes: uint32 n (<= 65535), uint32 final flag, the n bytes.
 //   kind 1, an image: uint32 height, row_bytes, bytes per pixel, filter mode (0..4, 5 adaptive),
 //           then height x row_bytes pixel bytes; it is cut into strips as the kernel cuts it.
+//   kind 2, a 16-bit grey image: the header of kind 1 with bytes per pixel 2, then height x
+//           row_bytes bytes of little-endian samples; the encoder filters their big-endian bytes.
 // Result file, per case: uint32 stream length, Adler-32 s1, s2 of the filtered bytes, the stream (for
 // an image: the strips' streams joined, the sums combined).  Every buffer is allocated at its exact
 // size -- a strip's slot at its bound of 10 + filtered bytes -- so that a read or write one byte
@@ -58,7 +60,7 @@ int main(int argc, char** argv) {
     uint32_t kind = 0;
     std::vector<uint8_t> stream;
     uint32_t s1 = 1, s2 = 0;
-    bool ok = read_exact(f, &kind, 4) && kind <= 1;
+    bool ok = read_exact(f, &kind, 4) && kind <= 2;
     if (ok && kind == 0) {
       uint32_t head[2];
       ok = read_exact(f, head, sizeof head) && head[0] <= kMaxStripBytes;
@@ -82,7 +84,8 @@ int main(int argc, char** argv) {
       ok = read_exact(f, head, sizeof head);
       const uint32_t height = head[0], row_bytes = head[1], bpp = head[2], mode = head[3];
       ok = ok && height >= 1 && height < (1u << 20) && row_bytes >= 1 && row_bytes < kMaxStripBytes &&
-           (bpp == 1 || bpp == 3) && row_bytes % bpp == 0 && mode <= kFilterAdaptive;
+           (kind == 2 ? bpp == 2 : (bpp == 1 || bpp == 3)) && row_bytes % bpp == 0 &&
+           mode <= kFilterAdaptive;
       if (ok) {
         std::unique_ptr<uint8_t[]> image(new uint8_t[(size_t)height * row_bytes]);   // exact size
         ok = read_exact(f, image.get(), (size_t)height * row_bytes);
@@ -98,7 +101,7 @@ int main(int argc, char** argv) {
           uint8_t* slot = static_cast<uint8_t*>(block);
           memset(shared.get(), 0xA5, sizeof(Shared));
           Encoder<HostPolicy> enc(policy, *shared, slot);
-          const uint32_t n = enc.filter(image.get(), row_bytes, bpp, mode, row0, rows);
+          const uint32_t n = enc.filter(image.get(), row_bytes, bpp, mode, row0, rows, kind == 2);
           ok = strip(enc, slot, n, row0 + rows == height, &stream);
           adler_combine(s1, s2, enc.s1(), enc.s2(), n, &s1, &s2);
         }
