@@ -727,6 +727,53 @@ int se3ds_png_inflate(const uint8_t* buf, int64_t buf_bytes, uint8_t* workspace,
 int se3ds_png_inflate_fields(void);
 int se3ds_png_inflate_ring_bytes(void);
 
+/* Baseline JPEG decode (ITU-T T.81: SOF0 / SOF1, 8 bit, Huffman, one interleaved scan) of a whole
+ * batch -- tf.image.decode_jpeg with its defaults (accurate integer DCT, fancy upscaling).
+ * csrc/jpeg.hip, decoder in csrc/jpeg_core.h.  The container is parsed by the caller
+ * (utils/jpeg.py); this call gets tables.
+ * buf: one device buffer of buf_bytes bytes, 8-byte aligned, that BEGINS with the device copy of the
+ * image table, then the segment table, and holds the entropy-coded bytes behind them.
+ * image table: int64 [n_images][se3ds_jpeg_decode_fields() = 200], `struct Image` of jpeg_core.h:
+ * width, height, components (1 or 3), horizontal and vertical sampling of component 0 (1 x 1, 2 x 1
+ * or 2 x 2; the others are 1 x 1; grey is 1 x 1), destination device pointer (height x width x
+ * channels uint8, dense), output channels (1 = the Y plane, 3 = RGB, a grey file replicated), byte
+ * offsets of the image's coefficients and of its component planes in workspace (16-byte aligned),
+ * first segment and segment count, MCUs per row and MCU rows, table selectors (bit c: DC table of
+ * component c, bit 4 + c: its AC table), two reserved words; then per component the 64
+ * quantisation values as uint16 in row-major order; then four Huffman tables (DC 0, DC 1, AC 0,
+ * AC 1) of 16 counts + 256 values each.
+ * segment table: int64 [n_segments][se3ds_jpeg_decode_segment_fields() = 5] = image, byte offset of
+ * the segment's entropy bytes in buf (not inside the tables; the RSTn marker is not part of it),
+ * their count, first MCU, MCU count.  A segment is a restart interval or the whole scan; the
+ * segments of an image are consecutive rows and cover its MCUs in order.
+ * workspace: device buffer, 16-byte aligned; se3ds_jpeg_decode_workspace_bytes(host_images, n) is
+ * the sum over the images of 128 bytes per block and of the planes padded to whole MCUs, each
+ * rounded up to 16.  Layout: the coefficients of all images, ascending and disjoint, then the planes
+ * of all images, likewise.
+ * phases: bit mask, 1 = entropy decode (the coefficients are zeroed first, then one workgroup of
+ * se3ds_jpeg_decode_lanes() threads per segment decodes it speculatively in windows of lanes x
+ * se3ds_jpeg_decode_chunk_bytes() bytes), 2 = dequantise + inverse DCT into the planes, 4 =
+ * upsample + colour + crop into the destinations.  Callers pass 7; a tool may time the parts.
+ * status_dev: device int32 [n_segments], written by phase 1: `enum class Status` of jpeg_core.h in
+ * the low 8 bits (0 = the segment held exactly its blocks), the rounds of all its windows in bits
+ * 8-30 (saturating).  Whatever the bytes say, the kernels read only inside the ranges given and
+ * write only inside the image's regions and destination.
+ * host_images, host_segments: the HOST copies, validated here before anything runs (BADSHAPE: a
+ * count < 1, n_images > 65535, a null or misaligned pointer, a range that leaves its buffer or
+ * enters the tables, regions out of order, sizes outside 1..65535, sampling or channels not listed
+ * above, MCU or segment counts that do not add up, Huffman counts that no prefix code has;
+ * WORKSPACE: workspace_bytes below the size above).  Integer arithmetic, no atomics, no host
+ * synchronisation: deterministic. */
+int se3ds_jpeg_decode(const uint8_t* buf, int64_t buf_bytes, uint8_t* workspace,
+                      int64_t workspace_bytes, const int64_t* host_images, int n_images,
+                      const int64_t* host_segments, int n_segments, int32_t* status_dev, int phases,
+                      void* stream);
+size_t se3ds_jpeg_decode_workspace_bytes(const int64_t* host_images, int n_images);
+int se3ds_jpeg_decode_fields(void);
+int se3ds_jpeg_decode_segment_fields(void);
+int se3ds_jpeg_decode_lanes(void);
+int se3ds_jpeg_decode_chunk_bytes(void);
+
 /* One uint8 image sheet from a batch of float images -- utils/image_grid.py:24-51 (get_grid_image:
  * tf.cast(x * 255.0, tf.uint8), then images_to_grid).  csrc/png_encode.hip.
  * src: (n, h, w, c) F32 / BF16, c 1 or 3.  out: uint8 (ny * h, nx * w, out_c), out_c 1 or 3; tile i

@@ -56,6 +56,12 @@ _SIGS = {
     'se3ds_png_inflate': (c_int, [c_p, c_i64, c_p, c_i64, c_p, c_int, c_p, c_p]),
     'se3ds_png_inflate_fields': (c_int, []),
     'se3ds_png_inflate_ring_bytes': (c_int, []),
+    'se3ds_jpeg_decode': (c_int, [c_p, c_i64, c_p, c_i64, c_p, c_int, c_p, c_int, c_p, c_int, c_p]),
+    'se3ds_jpeg_decode_workspace_bytes': (c_sz, [c_p, c_int]),
+    'se3ds_jpeg_decode_fields': (c_int, []),
+    'se3ds_jpeg_decode_segment_fields': (c_int, []),
+    'se3ds_jpeg_decode_lanes': (c_int, []),
+    'se3ds_jpeg_decode_chunk_bytes': (c_int, []),
     'se3ds_grid_quantize': (c_int, [c_p] + [c_int] * 8 + [c_p, c_p]),
     'se3ds_png_encode': (c_int, [c_p, c_p, c_int, c_p, c_i64, c_p, c_i64, c_p, c_int, c_p]),
     'se3ds_png_encode_workspace_bytes': (c_sz, [c_p, c_int]),

@@ -32,7 +32,7 @@ import torch
 
 from se3ds_amd import _lib, constants
 from se3ds_amd.datasets.indoor_datasets import IMAGE_PLANES, RAW_DTYPES
-from se3ds_amd.utils import png, tf_records
+from se3ds_amd.utils import jpeg, png, tf_records
 from se3ds_amd.utils.tf_bundle import _get_varint, _pb_bytes, _put_varint, crc32c, mask_crc
 
 # the order in which an Example's planes are written; `_parse` reads them by name
@@ -363,7 +363,10 @@ class R2RRecordWriter:
           bbox=(0, 0, 0, 0)):
     """Queues one example: device tensors in the raw dtypes of RAW_DTYPES -- image / proj_image uint8
     (H,W,3); depth / proj_depth int16 bit patterns of uint16 (H,W); proj_mask / blurred_mask /
-    segmentation uint8 (H,W).  An absent blurred_mask or segmentation is zeros.  The tensors are
+    segmentation uint8 (H,W).  An absent blurred_mask or segmentation is zeros.  `image` may also be
+    `bytes` holding a baseline JPEG file (utils/jpeg.py): its header is parsed here (ValueError unless
+    it decodes to (H,W,3) with depth's H, W) and the pixels are decoded at the flush, all pending
+    JPEGs in one `decode_jpeg_batch`, in front of the plane encode.  The tensors are
     copied into row-major order, so views of any strides (a permuted CHW image, a transposed plane)
     are taken as they index and the caller may reuse them.  The features written are those `R2RImageDataset._parse`
     reads (reference :149-178), under the names of IMAGE_PLANES."""
@@ -371,9 +374,14 @@ class R2RRecordWriter:
       raise ValueError('R2RRecordWriter: the writer is closed')
     planes = dict(image=image, depth=depth, proj_image=proj_image, proj_depth=proj_depth,
                   proj_mask=proj_mask, blurred_mask=blurred_mask, segmentation=segmentation)
+    scan = None
+    if isinstance(image, (bytes, bytearray, memoryview)):
+      # a JPEG file: the header is read now, the pixels are decoded with the flush's other JPEGs
+      scan = jpeg.parse_jpeg(bytes(image))
+      del planes['image']
     _lib.require_cuda(*planes.values())
     h, w = int(proj_mask.shape[0]), int(proj_mask.shape[1])
-    stored = {}
+    stored = {'image': scan} if scan is not None else {}
     for name, t in planes.items():
       channels = IMAGE_PLANES[name][1]
       if t is None:
@@ -387,6 +395,9 @@ class R2RRecordWriter:
       # a dense copy in row-major order, whatever the strides of what came in: the encoder reads
       # height x row_bytes bytes from the pointer
       stored[name] = t.reshape(h, w, channels).clone(memory_format=torch.contiguous_format)
+    if scan is not None and (scan.height, scan.width, scan.components) != (h, w, 3):   # (depth is (h, w))
+      raise ValueError(f'image: a JPEG that decodes to {(scan.height, scan.width, scan.components)}, '
+                       f'expected {(h, w, 3)}')
     self._pending.append(dict(planes=stored, scan_id=bytes(scan_id), filename=bytes(filename),
                               depth_scale=float(depth_scale), dataset_type=int(dataset_type),
                               bbox=tuple(float(b) for b in bbox)))
@@ -394,13 +405,24 @@ class R2RRecordWriter:
       self.flush()
 
   def flush(self):
-    """Encodes, assembles, checksums and writes the pending examples."""
+    """Encodes, assembles, checksums and writes the pending examples.  Images that came as JPEG files
+    are decoded first; if one of them does not decode, ValueError names it (its index among the pending
+    JPEGs), nothing is written and the pending examples stay queued."""
     if not self._pending:
       return
+    dev = self.device
+    decode_seconds = 0.0
+    encoded = [e for e in self._pending if isinstance(e['planes']['image'], jpeg.JpegScan)]
+    if encoded:
+      # 0: all in one decode, in front of taking the examples over (its status check synchronises)
+      t0 = time.perf_counter()
+      decoded = jpeg.decode_jpeg_batch([e['planes']['image'] for e in encoded], dev, channels=3)
+      for e, pixels in zip(encoded, decoded):
+        e['planes']['image'] = pixels
+      decode_seconds = time.perf_counter() - t0
     pending, self._pending = self._pending, []
     L = _lib.lib()
-    dev = self.device
-    clock = {}
+    clock = {'jpeg_decode': decode_seconds} if encoded else {}
     t0 = time.perf_counter()
 
     def lap(name):

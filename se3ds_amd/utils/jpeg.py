@@ -1,0 +1,404 @@
+"""Baseline JPEG files -> uint8 pixels on the device, without TensorFlow or an image library: the
+`tf.image.decode_jpeg(rgb.jpeg)` the VLN augmentation notebook starts from, and the container
+Matterport panoramas are distributed in.
+
+  parse_jpeg         the container on the host (NumPy): SOF0 / SOF1 at 8 bits, DQT, DHT, DRI, one
+                     interleaved SOS; the entropy segments are found, nothing is decoded.
+  decode_jpeg_batch  files of any mix of geometries -> one upload, one `se3ds_jpeg_decode`
+                     (csrc/jpeg.hip: speculative parallel Huffman decode per restart interval,
+                     slow-integer inverse DCT, fancy upsampling, colour), tensors (H, W, C) uint8.
+
+The arithmetic is libjpeg's defaults (JDCT_ISLOW, fancy upsampling), which `tf.image.decode_jpeg`
+documents as its defaults too; the tests pin it against Pillow.  Where a sample leaves [0, 255]
+before the clamp by more than a decoder's look-up table covers, this decoder saturates.
+
+There is no CPU fallback: a non-CUDA device raises Se3dsHipError."""
+import enum
+from typing import List, NamedTuple, Sequence, Tuple, Union
+
+import numpy as np
+import torch
+
+from se3ds_amd import _lib
+
+ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34,
+                   27, 20, 13, 6, 7, 14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44,
+                   51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63], np.int64)
+
+_SOF_KINDS = {0xC2: 'progressive', 0xC3: 'lossless', 0xC5: 'differential sequential',
+              0xC6: 'differential progressive', 0xC7: 'differential lossless',
+              0xC9: 'arithmetic-coded sequential', 0xCA: 'arithmetic-coded progressive',
+              0xCB: 'arithmetic-coded lossless', 0xCD: 'arithmetic-coded differential sequential',
+              0xCE: 'arithmetic-coded differential progressive',
+              0xCF: 'arithmetic-coded differential lossless'}
+
+
+class JpegScan(NamedTuple):
+  """A parsed baseline JPEG: geometry, tables and where the entropy segments lie in `data`."""
+  height: int
+  width: int
+  components: int                 # 1 or 3
+  h0: int                         # sampling of the first component (the others are 1 x 1); grey: 1, 1
+  v0: int
+  quant: np.ndarray               # (components, 64) uint16, row-major order
+  huffman: np.ndarray             # (4, 272) uint8: DC 0, DC 1, AC 0, AC 1; 16 counts + 256 values
+  tables: int                     # bit c: DC table of component c; bit 4 + c: its AC table
+  restart_interval: int           # MCUs per segment, 0 = one segment
+  segments: Tuple[Tuple[int, int], ...]   # (offset in data, length): the RSTn markers are not inside
+  data: bytes
+
+  @property
+  def mcus_x(self):
+    return -(-self.width // (8 * self.h0))
+
+  @property
+  def mcus_y(self):
+    return -(-self.height // (8 * self.v0))
+
+  @property
+  def blocks_per_mcu(self):
+    return 1 if self.components == 1 else self.h0 * self.v0 + 2
+
+
+def _segment(buf, p, what):
+  if p + 2 > len(buf):
+    raise ValueError(f'JPEG: the file ends inside {what}')
+  n = (buf[p] << 8) | buf[p + 1]
+  if n < 2 or p + n > len(buf):
+    raise ValueError(f'JPEG: the length of {what} leaves the file')
+  return buf[p + 2:p + n], p + n
+
+
+def parse_jpeg(buf: bytes) -> JpegScan:
+  """The container walk.  ValueError: not a well-formed file.  NotImplementedError naming the kind:
+  a well-formed file this decoder does not read."""
+  buf = bytes(buf)
+  if buf[:2] != b'\xff\xd8':
+    raise ValueError('JPEG: no SOI marker')
+  p, qt, ht, dri, frame, adobe = 2, {}, {}, 0, None, None
+  while True:
+    if p + 2 > len(buf):
+      raise ValueError('JPEG: no SOS marker' if frame else 'JPEG: no SOF marker')
+    if buf[p] != 0xFF:
+      raise ValueError(f'JPEG: no marker at byte {p}')
+    m = buf[p + 1]
+    if m == 0xFF:   # fill byte
+      p += 1
+      continue
+    p += 2
+    if m == 0xD8 or m == 0x01 or 0xD0 <= m <= 0xD7:
+      continue
+    if m == 0xD9:
+      raise ValueError('JPEG: no SOS marker' if frame else 'JPEG: no SOF marker')
+    if m in _SOF_KINDS:
+      raise NotImplementedError(f'JPEG: {_SOF_KINDS[m]} frames are not supported (baseline only)')
+    if m in (0xC0, 0xC1):
+      s, p = _segment(buf, p, 'SOF')
+      if frame is not None:
+        raise ValueError('JPEG: two SOF markers')
+      if len(s) < 6 or len(s) != 6 + 3 * s[5]:
+        raise ValueError('JPEG: the length of SOF does not fit its component count')
+      if s[0] == 12:
+        raise NotImplementedError('JPEG: 12-bit samples are not supported')
+      if s[0] != 8:
+        raise ValueError(f'JPEG: sample precision {s[0]}')
+      height, width, nc = (s[1] << 8) | s[2], (s[3] << 8) | s[4], s[5]
+      if height == 0 or width == 0 or nc == 0:
+        raise ValueError(f'JPEG: zero size ({height} x {width}, {nc} components)')
+      comps = [(s[6 + 3 * i], s[7 + 3 * i] >> 4, s[7 + 3 * i] & 15, s[8 + 3 * i]) for i in range(nc)]
+      if nc == 4:
+        raise NotImplementedError('JPEG: four components (CMYK / YCCK) are not supported')
+      if nc not in (1, 3):
+        raise NotImplementedError(f'JPEG: {nc} components are not supported')
+      if any(h == 0 or v == 0 or h > 4 or v > 4 or tq > 3 for _, h, v, tq in comps):
+        raise ValueError('JPEG: sampling factor or table number out of range in SOF')
+      frame = (height, width, comps)
+    elif m == 0xDB:
+      s, p = _segment(buf, p, 'DQT')
+      i = 0
+      while i < len(s):
+        pq, tq = s[i] >> 4, s[i] & 15
+        n = 128 if pq == 1 else 64
+        if pq > 1 or tq > 3 or i + 1 + n > len(s):
+          raise ValueError('JPEG: malformed DQT')
+        raw = np.frombuffer(s, np.uint8, n, i + 1)
+        vals = raw.astype(np.uint16) if pq == 0 else (raw[0::2].astype(np.uint16) << 8) | raw[1::2]
+        table = np.zeros(64, np.uint16)
+        table[ZIGZAG] = vals
+        qt[tq] = table
+        i += 1 + n
+    elif m == 0xC4:
+      s, p = _segment(buf, p, 'DHT')
+      i = 0
+      while i < len(s):
+        if i + 17 > len(s):
+          raise ValueError('JPEG: malformed DHT')
+        tc, th = s[i] >> 4, s[i] & 15
+        counts = np.frombuffer(s, np.uint8, 16, i + 1)
+        n, code = int(counts.sum()), 0
+        for l in range(16):
+          code += int(counts[l])
+          if code > (2 << l):
+            raise ValueError('JPEG: DHT counts that no prefix code has')
+          code <<= 1
+        if tc > 1 or th > 3 or n > 256 or i + 17 + n > len(s):
+          raise ValueError('JPEG: malformed DHT')
+        row = np.zeros(272, np.uint8)
+        row[:16] = counts
+        row[16:16 + n] = np.frombuffer(s, np.uint8, n, i + 17)
+        ht[(tc, th)] = row
+        i += 17 + n
+    elif m == 0xDD:
+      s, p = _segment(buf, p, 'DRI')
+      if len(s) != 2:
+        raise ValueError('JPEG: malformed DRI')
+      dri = (s[0] << 8) | s[1]
+    elif m == 0xEE:
+      s, p = _segment(buf, p, 'APP14')
+      if len(s) >= 12 and s[:5] == b'Adobe':
+        adobe = s[11]
+    elif m == 0xDA:
+      s, p = _segment(buf, p, 'SOS')
+      break
+    else:   # APPn, COM, DNL, ...: skipped
+      s, p = _segment(buf, p, f'marker {m:02X}')
+  if frame is None:
+    raise ValueError('JPEG: no SOF marker in front of SOS')
+  height, width, comps = frame
+  nc = len(comps)
+  if len(s) < 1 or len(s) != 4 + 2 * s[0]:
+    raise ValueError('JPEG: malformed SOS')
+  if s[0] != nc:
+    raise NotImplementedError('JPEG: more than one scan (non-interleaved components) is not supported')
+  sel = [(s[1 + 2 * i], s[2 + 2 * i] >> 4, s[2 + 2 * i] & 15) for i in range(nc)]
+  if [c for c, _, _ in sel] != [c[0] for c in comps]:
+    raise ValueError('JPEG: the components of SOS are not those of SOF')
+  if tuple(s[1 + 2 * nc:]) != (0, 63, 0):
+    raise ValueError('JPEG: spectral selection or approximation in a sequential scan')
+  if nc == 3 and (adobe == 0 or bytes(c[0] for c in comps) == b'RGB'):
+    raise NotImplementedError('JPEG: Adobe APP14 transform 0 (RGB components) is not supported')
+  if nc == 1:
+    h0 = v0 = 1   # one component: the scan is not interleaved, an MCU is one block
+  else:
+    h0, v0 = comps[0][1], comps[0][2]
+    if (h0, v0) not in ((1, 1), (2, 1), (2, 2)) or any((h, v) != (1, 1) for _, h, v, _ in comps[1:]):
+      kinds = ', '.join(f'{h}x{v}' for _, h, v, _ in comps)
+      raise NotImplementedError(f'JPEG: sampling {kinds} is not supported (4:4:4, 4:2:2 as 2x1 and '
+                                '4:2:0 as 2x2 are)')
+  quant = np.zeros((nc, 64), np.uint16)
+  for i, (_, _, _, tq) in enumerate(comps):
+    if tq not in qt:
+      raise ValueError(f'JPEG: quantisation table {tq} is missing')
+    quant[i] = qt[tq]
+  huffman, tables = np.zeros((4, 272), np.uint8), 0
+  for tc in (0, 1):
+    used = []
+    for i, one in enumerate(sel):
+      th = one[1 + tc]
+      if (tc, th) not in ht:
+        raise ValueError(f"JPEG: {'AC' if tc else 'DC'} Huffman table {th} is missing")
+      if th not in used:
+        used.append(th)
+      tables |= used.index(th) << (4 * tc + i) if used.index(th) < 2 else 0
+    if len(used) > 2:
+      raise NotImplementedError(f"JPEG: more than two {'AC' if tc else 'DC'} Huffman tables in one scan "
+                                'are not supported')
+    for slot, th in enumerate(used):
+      huffman[2 * tc + slot] = ht[(tc, th)]
+
+  # the entropy segments: an FF that no 00 follows is a marker
+  a = np.frombuffer(buf, np.uint8)
+  marks = np.flatnonzero((a[p:-1] == 0xFF) & (a[p + 1:] != 0)) + p
+  segments, start, end, expect, closed = [], p, None, 0, False
+  for pos in marks.tolist():
+    m = buf[pos + 1]
+    if end is None:
+      end = pos
+    if m == 0xFF:
+      continue
+    if 0xD0 <= m <= 0xD7:
+      if m - 0xD0 != expect:
+        raise ValueError(f'JPEG: RST{m - 0xD0} where RST{expect} is due')
+      expect = (expect + 1) & 7
+      segments.append((start, end - start))
+      start, end = pos + 2, None
+    elif m == 0xD9:
+      segments.append((start, end - start))
+      closed = True
+      break
+    elif m in (0xDA, 0xC4, 0xDB, 0xDD):
+      raise NotImplementedError('JPEG: more than one scan is not supported')
+    else:
+      raise ValueError(f'JPEG: marker {m:02X} inside the scan')
+  if not closed:
+    raise ValueError('JPEG: no EOI marker')
+  mcus = -(-width // (8 * h0)) * -(-height // (8 * v0))
+  want = -(-mcus // dri) if dri else 1
+  if len(segments) != want:
+    raise ValueError(f'JPEG: {len(segments)} entropy segments where the geometry and DRI = {dri} give {want}')
+  return JpegScan(height, width, nc, h0, v0, quant, huffman, tables, dri, tuple(segments), buf)
+
+
+# --------------------------------------------------------------------------------- the device
+class JpegStatus(enum.IntEnum):
+  """`enum class Status` of csrc/jpeg_core.h."""
+  OK = 0
+  TRUNCATED = 1
+  BAD_CODE = 2
+  BAD_RUN = 3
+  BAD_DC = 4
+  TOO_LONG = 5
+
+
+_REASONS = {
+    JpegStatus.TRUNCATED: 'the entropy-coded bits end before the last block',
+    JpegStatus.BAD_CODE: 'bits that are no Huffman code word',
+    JpegStatus.BAD_RUN: 'a zero run past coefficient 63',
+    JpegStatus.BAD_DC: 'a DC difference category above 11',
+    JpegStatus.TOO_LONG: 'entropy-coded bytes behind the last block',
+}
+
+
+def jpeg_failure(word: int) -> str:
+  """The message of a non-zero status code of se3ds_jpeg_decode."""
+  return f'the scan does not decode: {_REASONS[JpegStatus(word & 0xff)]}'
+
+
+def status_rounds(words) -> np.ndarray:
+  """The round counts in the status words of se3ds_jpeg_decode."""
+  return (np.asarray(words).astype(np.int64) >> 8) & 0x7fffff
+
+
+class PendingJpegDecode:
+  """One batch in flight: `check()` waits for the status words and raises ValueError for the first
+  image with a segment that failed.  The tensors count only once it has returned.  `words` (after
+  check or wait): the status word of every segment; `segment_image`: the image of each."""
+
+  def __init__(self, event, status, segment_image):
+    self._event, self._status, self.segment_image = event, status, segment_image
+
+  def wait(self) -> np.ndarray:
+    self._event.synchronize()
+    return self._status.numpy()
+
+  @property
+  def words(self) -> np.ndarray:
+    return self.wait()
+
+  def check(self) -> None:
+    words = self.wait()
+    bad = np.flatnonzero(words & 0xff)
+    if bad.size:
+      s = int(bad[0])
+      raise ValueError(f'image {int(self.segment_image[s])}: {jpeg_failure(int(words[s]))}')
+
+
+def output_channels(scan: JpegScan, channels: int) -> int:
+  if channels not in (0, 1, 3):
+    raise ValueError(f'channels: 0 (the file\'s), 1 or 3, got {channels!r}')
+  return channels or scan.components
+
+
+def _aligned(n: int) -> int:
+  return (n + 15) & ~15
+
+
+class JpegBatch:
+  """The tables, the uploaded bytes, the workspace and the output tensors of one batch, on the current
+  stream of `device`: `launch(phases)` queues `se3ds_jpeg_decode` on them (the timing tool launches
+  more than once), `pending()` queues the copy of the status words."""
+
+  def __init__(self, scans: Sequence[JpegScan], dev, channels: int = 0):
+    out_c = [output_channels(s, channels) for s in scans]
+    L = _lib.lib()
+    n = len(scans)
+    fields, seg_fields = L.se3ds_jpeg_decode_fields(), L.se3ds_jpeg_decode_segment_fields()
+    n_seg = sum(len(s.segments) for s in scans)
+    images = np.zeros((n, fields), np.int64)
+    segments = np.zeros((n_seg, seg_fields), np.int64)
+    image_bytes = images.view(np.uint8).reshape(n, fields * 8)
+    offset = _aligned(images.nbytes + segments.nbytes)
+    coef_sizes, plane_sizes, spans, at = [], [], [], 0
+    for i, s in enumerate(scans):
+      images[i, :5] = (s.width, s.height, s.components, s.h0, s.v0)
+      images[i, 6] = out_c[i]
+      images[i, 9:14] = (at, len(s.segments), s.mcus_x, s.mcus_y, s.tables)
+      image_bytes[i, 128:128 + 128 * s.components] = s.quant.view(np.uint8).reshape(-1)
+      image_bytes[i, 512:] = s.huffman.reshape(-1)
+      coef_sizes.append(_aligned(s.mcus_x * s.mcus_y * s.blocks_per_mcu * 128))
+      planes = s.mcus_x * s.h0 * 8 * s.mcus_y * s.v0 * 8
+      if s.components == 3:
+        planes += 2 * s.mcus_x * 8 * s.mcus_y * 8
+      plane_sizes.append(_aligned(planes))
+      # the segments of a file lie in it one behind the other, RSTn markers between: one copy
+      first, last = s.segments[0][0], s.segments[-1][0] + s.segments[-1][1]
+      spans.append((offset, first, last))
+      mcus, step, mcu = s.mcus_x * s.mcus_y, s.restart_interval or s.mcus_x * s.mcus_y, 0
+      for k, (seg_at, seg_len) in enumerate(s.segments):
+        segments[at + k] = (i, offset + seg_at - first, seg_len, mcu, min(step, mcus - mcu))
+        mcu += step
+      at += len(s.segments)
+      offset = _aligned(offset + last - first)
+    # the workspace: every image's coefficients, then every image's planes
+    coef_at = np.concatenate([[0], np.cumsum(coef_sizes)])
+    plane_at = coef_at[-1] + np.concatenate([[0], np.cumsum(plane_sizes)])
+    images[:, 7], images[:, 8] = coef_at[:-1], plane_at[:-1]
+    self.workspace_bytes, self.buf_bytes = int(plane_at[-1]), offset
+    self.images, self.segments, self.device = images, segments, dev
+    with torch.cuda.device(dev):
+      self.out = [torch.empty((s.height, s.width, c), dtype=torch.uint8, device=dev)
+                  for s, c in zip(scans, out_c)]
+      images[:, 5] = [t.data_ptr() for t in self.out]
+      need = L.se3ds_jpeg_decode_workspace_bytes(images.ctypes.data, n)   # 0: the launch says why
+      assert need in (0, self.workspace_bytes), f'workspace layout: {self.workspace_bytes}, library {need}'
+      staging = torch.empty((offset,), dtype=torch.uint8, pin_memory=True)
+      host = staging.numpy()
+      host[:images.nbytes] = images.reshape(-1).view(np.uint8)
+      host[images.nbytes:images.nbytes + segments.nbytes] = segments.reshape(-1).view(np.uint8)
+      for s, (to, first, last) in zip(scans, spans):
+        host[to:to + last - first] = np.frombuffer(s.data, np.uint8, last - first, first)
+      self.device_buf = staging.to(dev, non_blocking=True)
+      self.workspace = torch.empty((max(self.workspace_bytes, 16),), dtype=torch.uint8, device=dev)
+      self.status = torch.zeros((n_seg,), dtype=torch.int32, device=dev)
+
+  def launch(self, phases: int = 7) -> None:
+    with torch.cuda.device(self.device):
+      rc = _lib.lib().se3ds_jpeg_decode(
+          _lib.ptr(self.device_buf), self.buf_bytes, _lib.ptr(self.workspace), self.workspace_bytes,
+          self.images.ctypes.data, len(self.images), self.segments.ctypes.data, len(self.segments),
+          _lib.ptr(self.status), phases, _lib.stream())
+    _lib.check(rc, 'se3ds_jpeg_decode')
+
+  def pending(self) -> PendingJpegDecode:
+    with torch.cuda.device(self.device):
+      status_host = torch.empty((len(self.segments),), dtype=torch.int32, pin_memory=True)
+      status_host.copy_(self.status, non_blocking=True)
+      event = torch.cuda.Event()
+      event.record()
+    return PendingJpegDecode(event, status_host, self.segments[:, 0].copy())
+
+
+def decode_jpeg_batch(bufs: Sequence[Union[bytes, JpegScan]], device, channels: int = 0,
+                      check: bool = True):
+  """Encoded JPEG files (or JpegScans of parse_jpeg) -> a list of uint8 tensors (H, W, C) on `device`,
+  the shape tf.image.decode_jpeg gives.  channels: 0 = the file's, 3 replicates a grey file, 1 gives
+  the Y plane of a colour file at full size.  Mixed geometries share the call: the tables and the
+  entropy bytes of all files go up in one pinned buffer and one copy, and `se3ds_jpeg_decode` queues
+  a memset and three launches on the current stream.  check=True reads the status words back (one
+  synchronisation) and raises ValueError naming the image and the reason; check=False returns
+  (tensors, PendingJpegDecode)."""
+  dev = torch.device(device)
+  if dev.type != 'cuda':
+    raise _lib.Se3dsHipError(f'decode_jpeg_batch decodes on an MI355X (cuda) device; got {dev}.  '
+                             'There is no CPU fallback.')
+  if dev.index is None:
+    dev = torch.device('cuda', torch.cuda.current_device())
+  if len(bufs) == 0:
+    raise ValueError('decode_jpeg_batch: nothing to decode')
+  batch = JpegBatch([b if isinstance(b, JpegScan) else parse_jpeg(b) for b in bufs], dev, channels)
+  batch.launch(7)
+  pending = batch.pending()
+  if not check:
+    return batch.out, pending
+  pending.check()
+  return batch.out
