@@ -33,6 +33,7 @@ from se3ds_amd import _lib
 from se3ds_amd import constants
 from se3ds_amd import gin_lite as gin
 from se3ds_amd.utils import png
+from se3ds_amd.utils._staging import cuda_device
 from se3ds_amd.utils import tf_records
 from se3ds_amd.utils.tf_records import FixedLenFeature
 
@@ -302,10 +303,7 @@ class R2RImageDataset:
     if batch_size <= 0:
       raise ValueError(f'batch_size {batch_size}')
     png.check_inflate_mode(inflate)
-    dev = torch.device(device if device is not None else f'cuda:{torch.cuda.current_device()}')
-    if dev.type != 'cuda':
-      raise _lib.Se3dsHipError(f'input_fn decodes and transforms on an MI355X (cuda) device; got {dev}.'
-                               '  There is no CPU fallback.')
+    dev = cuda_device(device, 'input_fn', 'decodes and transforms')
     files = _record_files(self.get_file_patterns(split, file_pattern))
     local_seed = seed + input_pipeline_id
     draw_rng = np.random.default_rng(local_seed)

@@ -33,6 +33,7 @@ import torch
 from se3ds_amd import _lib, constants
 from se3ds_amd.datasets.indoor_datasets import IMAGE_PLANES, RAW_DTYPES
 from se3ds_amd.utils import jpeg, png, tf_records
+from se3ds_amd.utils._staging import Readback, cuda_device, upload
 from se3ds_amd.utils.tf_bundle import _get_varint, _pb_bytes, _put_varint, crc32c, mask_crc
 
 # the order in which an Example's planes are written; `_parse` reads them by name
@@ -286,10 +287,6 @@ def patch_crc(out: torch.Tensor, crcs: torch.Tensor, patches) -> None:
 
 
 # ------------------------------------------------------------------------------ the writer
-def _aligned(n: int) -> int:
-  return (n + 15) & ~15
-
-
 class R2RRecordWriter:
   """Context manager that writes training Examples to `path` (a `train*.tfrecord` file of
   `R2RImageDataset`), encoded and assembled on `device`.  `add` queues an example; every
@@ -302,12 +299,7 @@ class R2RRecordWriter:
 
   def __init__(self, path: str, device, filters='adaptive', examples_per_flush: int = 8,
                profile: bool = False):
-    dev = torch.device(device)
-    if dev.type != 'cuda':
-      raise _lib.Se3dsHipError(f'R2RRecordWriter encodes on an MI355X (cuda) device; got {dev}.  '
-                               'There is no CPU fallback.')
-    if dev.index is None:
-      dev = torch.device('cuda', torch.cuda.current_device())
+    dev = cuda_device(device, 'R2RRecordWriter', 'encodes')
     if examples_per_flush < 1:
       raise ValueError(f'examples_per_flush {examples_per_flush}')
     self.path, self.device, self.examples_per_flush = path, dev, int(examples_per_flush)
@@ -436,7 +428,9 @@ class R2RRecordWriter:
     with torch.cuda.device(dev):
       # 1-2: every plane of every example in one encode; the sizes come back
       tensors = [e['planes'][name] for e in pending for name in _PLANE_ORDER]
-      table, sizes, result, head = _encode_planes(tensors, self._mode)
+      # (the planes include 16-bit depth, so launch_encode takes se3ds_png_encode_planes, always)
+      table, result, head = png.launch_encode(tensors, [self._mode] * len(tensors))
+      sizes = result[:8 * len(tensors)].cpu().numpy().view(np.uint32).reshape(-1, 2)   # waits
       lap('encode')
       # 3: the layout, from sizes alone
       payloads, k = [], 0
@@ -465,18 +459,9 @@ class R2RRecordWriter:
       patchc_table[1::2, 1] = frames[:, 0] + 12 + frames[:, 1]
       patchc_table[:, 2] = 1
       # one upload: the literals, then the five tables, each 16-byte aligned
-      parts = [np.frombuffer(bytes(layout.literals), np.uint8)] + [
-          t.reshape(-1).view(np.uint8) for t in (seg, crcz_table, patchz_table, crcc_table, patchc_table)]
-      at, offsets = 0, []
-      for p in parts:
-        offsets.append(at)
-        at = _aligned(at + p.size)
-      staging = torch.empty((at,), dtype=torch.uint8, pin_memory=True)
-      host = staging.numpy()
-      for o, p in zip(offsets, parts):
-        host[o:o + p.size] = p
-      upload = staging.to(dev, non_blocking=True)
-      base = upload.data_ptr()
+      uploaded, offsets = upload([layout.literals, seg, crcz_table, patchz_table, crcc_table,
+                                  patchc_table], dev)
+      base = uploaded.data_ptr()
       out = torch.empty((layout.total,), dtype=torch.uint8, device=dev)
       crcs = torch.empty((max(n_idat, 2 * n_rec),), dtype=torch.int32, device=dev)
       stream = _lib.stream()
@@ -507,43 +492,17 @@ class R2RRecordWriter:
                                    stream), 'se3ds_patch_crc')
       lap('record_crc')
       # 9: the finished bytes
-      done = torch.empty((layout.total,), dtype=torch.uint8, pin_memory=True)
-      done.copy_(out, non_blocking=True)
-      torch.cuda.current_stream().synchronize()
+      done = Readback(out).wait()
       if self._profile:
         now = time.perf_counter()
         clock['download'] = now - t0
         t0 = now
-    self._file.write(done.numpy().data)
+    self._file.write(done.data)
     if self._profile:
       clock['file_write'] = time.perf_counter() - t0
       self.timings.append(clock)
     self.examples += len(pending)
     self.bytes_written += layout.total
-
-
-def _encode_planes(tensors: Sequence[torch.Tensor], mode: int):
-  """`png.encode_streams` without the download of the streams: -> (table, sizes on the host, the
-  device buffer [sizes | streams], offset of the streams in it).  The first synchronisation of a
-  flush is the copy of the sizes."""
-  L = _lib.lib()
-  n = len(tensors)
-  dev = tensors[0].device
-  table = png.encode_table([t.data_ptr() for t in tensors], [png.plane_geometry(t) for t in tensors],
-                           [mode] * n)
-  workspace_bytes = L.se3ds_png_encode_planes_workspace_bytes(table.ctypes.data, n)
-  out_bytes = L.se3ds_png_encode_planes_out_bytes(table.ctypes.data, n)
-  head = _aligned(8 * n)
-  staging = torch.from_numpy(table.reshape(-1)).pin_memory()
-  table_dev = staging.to(dev, non_blocking=True)
-  workspace = torch.empty((max(workspace_bytes, 16),), dtype=torch.uint8, device=dev)
-  result = torch.empty((head + out_bytes,), dtype=torch.uint8, device=dev)
-  rc = L.se3ds_png_encode_planes(_lib.ptr(table_dev), table.ctypes.data, n, _lib.ptr(workspace),
-                                 workspace_bytes, _lib.ptr(result) + head, out_bytes, _lib.ptr(result),
-                                 3, _lib.stream())
-  _lib.check(rc, 'se3ds_png_encode_planes')
-  sizes = result[:8 * n].cpu().numpy().view(np.uint32).reshape(n, 2)   # waits for the stream
-  return table, sizes, result, head
 
 
 # --------------------------------------------------------------------------- trajectories

@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from se3ds_amd import _lib
+from se3ds_amd.utils._staging import cuda_device
 
 SLAB_ALIGN = 16   # items start on 16-byte boundaries of their slab
 
@@ -128,10 +129,7 @@ def crc32c_host_slabs(items, slab_bytes: int = 256 << 20, device=None) -> np.nda
   latter as they lie in memory), in input order.  The items are packed into slabs of at most
   `slab_bytes`, each uploaded once and checked with one device call, so the host memory in flight is
   one slab whatever the total."""
-  dev = torch.device(device if device is not None else f'cuda:{torch.cuda.current_device()}')
-  if dev.type != 'cuda':
-    raise _lib.Se3dsHipError(f'crc32c_host_slabs computes on an MI355X (cuda) device; got {dev}.'
-                             '  There is no CPU fallback.')
+  dev = cuda_device(device, 'crc32c_host_slabs')
   views = [_as_bytes(x) for x in items]
   out = np.zeros((len(views),), np.uint32)
   for idx, offs, used in pack_slabs([v.size for v in views], slab_bytes):

@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from se3ds_amd import _lib
+from se3ds_amd.utils._staging import Readback, cuda_device, layout, upload
 
 ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34,
                    27, 20, 13, 6, 7, 14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44,
@@ -269,17 +270,14 @@ def status_rounds(words) -> np.ndarray:
   return (np.asarray(words).astype(np.int64) >> 8) & 0x7fffff
 
 
-class PendingJpegDecode:
+class PendingJpegDecode(Readback):
   """One batch in flight: `check()` waits for the status words and raises ValueError for the first
   image with a segment that failed.  The tensors count only once it has returned.  `words` (after
   check or wait): the status word of every segment; `segment_image`: the image of each."""
 
-  def __init__(self, event, status, segment_image):
-    self._event, self._status, self.segment_image = event, status, segment_image
-
-  def wait(self) -> np.ndarray:
-    self._event.synchronize()
-    return self._status.numpy()
+  def __init__(self, status: torch.Tensor, segment_image):
+    super().__init__(status)   # the status words on the device: their copy and its event are queued
+    self.segment_image = segment_image
 
   @property
   def words(self) -> np.ndarray:
@@ -299,10 +297,6 @@ def output_channels(scan: JpegScan, channels: int) -> int:
   return channels or scan.components
 
 
-def _aligned(n: int) -> int:
-  return (n + 15) & ~15
-
-
 class JpegBatch:
   """The tables, the uploaded bytes, the workspace and the output tensors of one batch, on the current
   stream of `device`: `launch(phases)` queues `se3ds_jpeg_decode` on them (the timing tool launches
@@ -317,33 +311,31 @@ class JpegBatch:
     images = np.zeros((n, fields), np.int64)
     segments = np.zeros((n_seg, seg_fields), np.int64)
     image_bytes = images.view(np.uint8).reshape(n, fields * 8)
-    offset = _aligned(images.nbytes + segments.nbytes)
-    coef_sizes, plane_sizes, spans, at = [], [], [], 0
+    # the segments of a file lie in it one behind the other, RSTn markers between: one span a file,
+    # behind the two tables
+    spans = [memoryview(s.data)[s.segments[0][0]:s.segments[-1][0] + s.segments[-1][1]] for s in scans]
+    offsets, self.buf_bytes = layout([images.nbytes + segments.nbytes] + [len(b) for b in spans])
+    coef_sizes, plane_sizes, at = [], [], 0
     for i, s in enumerate(scans):
       images[i, :5] = (s.width, s.height, s.components, s.h0, s.v0)
       images[i, 6] = out_c[i]
       images[i, 9:14] = (at, len(s.segments), s.mcus_x, s.mcus_y, s.tables)
       image_bytes[i, 128:128 + 128 * s.components] = s.quant.view(np.uint8).reshape(-1)
       image_bytes[i, 512:] = s.huffman.reshape(-1)
-      coef_sizes.append(_aligned(s.mcus_x * s.mcus_y * s.blocks_per_mcu * 128))
+      coef_sizes.append(s.mcus_x * s.mcus_y * s.blocks_per_mcu * 128)
       planes = s.mcus_x * s.h0 * 8 * s.mcus_y * s.v0 * 8
       if s.components == 3:
         planes += 2 * s.mcus_x * 8 * s.mcus_y * 8
-      plane_sizes.append(_aligned(planes))
-      # the segments of a file lie in it one behind the other, RSTn markers between: one copy
-      first, last = s.segments[0][0], s.segments[-1][0] + s.segments[-1][1]
-      spans.append((offset, first, last))
+      plane_sizes.append(planes)
+      first = s.segments[0][0]
       mcus, step, mcu = s.mcus_x * s.mcus_y, s.restart_interval or s.mcus_x * s.mcus_y, 0
       for k, (seg_at, seg_len) in enumerate(s.segments):
-        segments[at + k] = (i, offset + seg_at - first, seg_len, mcu, min(step, mcus - mcu))
+        segments[at + k] = (i, offsets[1 + i] + seg_at - first, seg_len, mcu, min(step, mcus - mcu))
         mcu += step
       at += len(s.segments)
-      offset = _aligned(offset + last - first)
     # the workspace: every image's coefficients, then every image's planes
-    coef_at = np.concatenate([[0], np.cumsum(coef_sizes)])
-    plane_at = coef_at[-1] + np.concatenate([[0], np.cumsum(plane_sizes)])
-    images[:, 7], images[:, 8] = coef_at[:-1], plane_at[:-1]
-    self.workspace_bytes, self.buf_bytes = int(plane_at[-1]), offset
+    workspace_at, self.workspace_bytes = layout(coef_sizes + plane_sizes)
+    images[:, 7], images[:, 8] = workspace_at[:n], workspace_at[n:]
     self.images, self.segments, self.device = images, segments, dev
     with torch.cuda.device(dev):
       self.out = [torch.empty((s.height, s.width, c), dtype=torch.uint8, device=dev)
@@ -351,13 +343,8 @@ class JpegBatch:
       images[:, 5] = [t.data_ptr() for t in self.out]
       need = L.se3ds_jpeg_decode_workspace_bytes(images.ctypes.data, n)   # 0: the launch says why
       assert need in (0, self.workspace_bytes), f'workspace layout: {self.workspace_bytes}, library {need}'
-      staging = torch.empty((offset,), dtype=torch.uint8, pin_memory=True)
-      host = staging.numpy()
-      host[:images.nbytes] = images.reshape(-1).view(np.uint8)
-      host[images.nbytes:images.nbytes + segments.nbytes] = segments.reshape(-1).view(np.uint8)
-      for s, (to, first, last) in zip(scans, spans):
-        host[to:to + last - first] = np.frombuffer(s.data, np.uint8, last - first, first)
-      self.device_buf = staging.to(dev, non_blocking=True)
+      tables = np.concatenate([images.reshape(-1), segments.reshape(-1)])
+      self.device_buf, _ = upload([tables] + spans, dev)
       self.workspace = torch.empty((max(self.workspace_bytes, 16),), dtype=torch.uint8, device=dev)
       self.status = torch.zeros((n_seg,), dtype=torch.int32, device=dev)
 
@@ -370,12 +357,7 @@ class JpegBatch:
     _lib.check(rc, 'se3ds_jpeg_decode')
 
   def pending(self) -> PendingJpegDecode:
-    with torch.cuda.device(self.device):
-      status_host = torch.empty((len(self.segments),), dtype=torch.int32, pin_memory=True)
-      status_host.copy_(self.status, non_blocking=True)
-      event = torch.cuda.Event()
-      event.record()
-    return PendingJpegDecode(event, status_host, self.segments[:, 0].copy())
+    return PendingJpegDecode(self.status, self.segments[:, 0].copy())
 
 
 def decode_jpeg_batch(bufs: Sequence[Union[bytes, JpegScan]], device, channels: int = 0,
@@ -387,12 +369,7 @@ def decode_jpeg_batch(bufs: Sequence[Union[bytes, JpegScan]], device, channels: 
   a memset and three launches on the current stream.  check=True reads the status words back (one
   synchronisation) and raises ValueError naming the image and the reason; check=False returns
   (tensors, PendingJpegDecode)."""
-  dev = torch.device(device)
-  if dev.type != 'cuda':
-    raise _lib.Se3dsHipError(f'decode_jpeg_batch decodes on an MI355X (cuda) device; got {dev}.  '
-                             'There is no CPU fallback.')
-  if dev.index is None:
-    dev = torch.device('cuda', torch.cuda.current_device())
+  dev = cuda_device(device, 'decode_jpeg_batch', 'decodes')
   if len(bufs) == 0:
     raise ValueError('decode_jpeg_batch: nothing to decode')
   batch = JpegBatch([b if isinstance(b, JpegScan) else parse_jpeg(b) for b in bufs], dev, channels)

@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from se3ds_amd import _lib
+from se3ds_amd.utils._staging import Readback, aligned, cuda_device, layout, upload
 
 SIGNATURE = b'\x89PNG\r\n\x1a\n'
 MAX_THREADS = 16
@@ -147,6 +148,29 @@ def _as_plane(item: Union[bytes, PngPlane]) -> PngPlane:
   return item if isinstance(item, PngPlane) else parse_png(item)
 
 
+def _plan(bufs_by_key, dev, parse):
+  """The front both decoders share: -> (out, rows).  `parse` turns the items of all keys, in key
+  order, into PngPlanes or PngStreams; geometry is checked within each key; out[key] is allocated on
+  `dev`; rows holds (key, index within the key, parsed item, address of its plane in out[key])."""
+  if not bufs_by_key or any(len(v) == 0 for v in bufs_by_key.values()):
+    raise ValueError('decode_png_batch: nothing to decode')
+  items = parse([item for bufs in bufs_by_key.values() for item in bufs])
+  out, rows = {}, []
+  for k, bufs in bufs_by_key.items():
+    group = items[len(rows):len(rows) + len(bufs)]
+    p0 = group[0]
+    for p in group:
+      if p[:4] != p0[:4]:
+        raise ValueError(f'{k}: a {p.height}x{p.width} PNG of {p.channels} channels at bit depth '
+                         f'{p.bit_depth} in a batch of {p0.height}x{p0.width}, {p0.channels}, '
+                         f'{p0.bit_depth}')
+    shape = (len(group), p0.height, p0.width) + ((3,) if p0.channels == 3 else ())
+    out[k] = torch.empty(shape, dtype=torch.int16 if p0.bit_depth == 16 else torch.uint8, device=dev)
+    plane_bytes = p0.height * p0.row_bytes
+    rows += [(k, i, p, out[k].data_ptr() + i * plane_bytes) for i, p in enumerate(group)]
+  return out, rows
+
+
 def decode_png_batch(bufs_by_key: Dict[str, Sequence[Union[bytes, PngPlane, PngStream]]], device,
                      threads: int = 4, inflate: str = 'host') -> Dict[str, torch.Tensor]:
   """{key: the N PNGs of one plane of a batch} -> {key: CUDA tensor}: uint8 (N,H,W,3) for RGB,
@@ -167,57 +191,26 @@ def decode_png_batch(bufs_by_key: Dict[str, Sequence[Union[bytes, PngPlane, PngS
     out, pending = decode_png_batch_async(bufs_by_key, device)
     pending.check()
     return out
-  dev = torch.device(device)
-  if dev.type != 'cuda':
-    raise _lib.Se3dsHipError('decode_png_batch reconstructs on an MI355X (cuda) device; got '
-                             f'{dev}.  There is no CPU fallback.')
-  if dev.index is None:
-    dev = torch.device('cuda', torch.cuda.current_device())
-  if not bufs_by_key or any(len(v) == 0 for v in bufs_by_key.values()):
-    raise ValueError('decode_png_batch: nothing to decode')
+  dev = cuda_device(device, 'decode_png_batch', 'reconstructs')
   threads = max(1, min(int(threads), MAX_THREADS))
-  keys = list(bufs_by_key)
-  flat = [item for k in keys for item in bufs_by_key[k]]
-  if all(isinstance(item, PngPlane) for item in flat):
-    planes = flat
-  else:
+
+  def parse(flat):
+    if all(isinstance(item, PngPlane) for item in flat):
+      return flat
     with concurrent.futures.ThreadPoolExecutor(max_workers=threads) as pool:
-      planes = list(pool.map(_as_plane, flat))
+      return list(pool.map(_as_plane, flat))
 
+  out, rows = _plan(bufs_by_key, dev, parse)
   L = _lib.lib()
-  fields = L.se3ds_png_unfilter_fields()
-  table = np.zeros((len(planes), fields), np.int64)
-  offset = (table.nbytes + 15) & ~15     # the streams follow the table, 16-byte aligned
-  out, idx = {}, 0
-  for k in keys:
-    group = planes[idx:idx + len(bufs_by_key[k])]
-    p0 = group[0]
-    for p in group:
-      if p[:4] != p0[:4]:
-        raise ValueError(f'{k}: a {p.height}x{p.width} PNG of {p.channels} channels at bit depth '
-                         f'{p.bit_depth} in a batch of {p0.height}x{p0.width}, {p0.channels}, '
-                         f'{p0.bit_depth}')
-    shape = (len(group), p0.height, p0.width) + ((3,) if p0.channels == 3 else ())
-    out[k] = torch.empty(shape, dtype=torch.int16 if p0.bit_depth == 16 else torch.uint8, device=dev)
-    plane_bytes = p0.height * p0.row_bytes
-    for i, p in enumerate(group):
-      table[idx + i] = (offset, out[k].data_ptr() + i * plane_bytes, p.height, p.row_bytes,
-                        p.bytes_per_pixel, int(p.bit_depth == 16))
-      offset += (len(p.filtered) + 15) & ~15
-    idx += len(group)
-
+  table = np.zeros((len(rows), L.se3ds_png_unfilter_fields()), np.int64)
+  # the device buffer starts with the table, and the table's offsets count from its base
+  offsets, _ = layout([table.nbytes] + [len(p.filtered) for _, _, p, _ in rows])
+  for i, (_, _, p, to) in enumerate(rows):
+    table[i] = (offsets[1 + i], to, p.height, p.row_bytes, p.bytes_per_pixel, int(p.bit_depth == 16))
   with torch.cuda.device(dev):
-    staging = torch.empty((offset,), dtype=torch.uint8, pin_memory=True)
-    host = staging.numpy()
-    host[:table.nbytes] = table.reshape(-1).view(np.uint8)
-    for row, p in zip(table, planes):
-      host[row[0]:row[0] + len(p.filtered)] = np.frombuffer(p.filtered, np.uint8)
-    # one copy: the device buffer starts with the table, and the table's offsets count from its base.
-    # Copy and kernel are queued on the current stream; the caching allocators (pinned and device)
-    # hand a freed block out again only behind that work.
-    device_buf = staging.to(dev, non_blocking=True)
-    rc = L.se3ds_png_unfilter(_lib.ptr(device_buf), offset, _lib.ptr(device_buf), table.ctypes.data,
-                              len(planes), _lib.stream())
+    device_buf, _ = upload([table] + [p.filtered for _, _, p, _ in rows], dev)
+    rc = L.se3ds_png_unfilter(_lib.ptr(device_buf), device_buf.numel(), _lib.ptr(device_buf),
+                              table.ctypes.data, len(rows), _lib.stream())
     _lib.check(rc, 'se3ds_png_unfilter')
   return out
 
@@ -276,17 +269,17 @@ def inflate_failure(word: int, stream: PngStream) -> str:
   return f'{more} inflated bytes than {stream.height} x (1 + {stream.row_bytes})'
 
 
-class PendingDecode:
+class PendingDecode(Readback):
   """The device inflate of one batch in flight: `check()` waits for the status words and raises
   ValueError for the first plane that failed.  The output tensors are valid (and may be read on the
   stream the batch was launched on) only if check() returns."""
 
-  def __init__(self, event, status, names: List[Tuple[str, int]], streams: List[PngStream]):
-    self._event, self._status, self._names, self._streams = event, status, names, streams
+  def __init__(self, status: torch.Tensor, names: List[Tuple[str, int]], streams: List[PngStream]):
+    super().__init__(status)   # the status words on the device: their copy and its event are queued
+    self._names, self._streams = names, streams
 
   def check(self) -> None:
-    self._event.synchronize()
-    words = self._status.numpy()
+    words = self.wait()
     bad = np.flatnonzero(words)
     if bad.size:
       i = int(bad[0])
@@ -312,68 +305,37 @@ def decode_png_batch_async(bufs_by_key: Dict[str, Sequence[Union[bytes, PngStrea
   event behind them.  `pending.check()` waits on that event and raises ValueError naming key, index
   within the key and reason for the first plane whose stream did not inflate to its geometry; `out`
   counts only once it has returned.  A non-CUDA device raises Se3dsHipError."""
-  dev = torch.device(device)
-  if dev.type != 'cuda':
-    raise _lib.Se3dsHipError('decode_png_batch inflates and reconstructs on an MI355X (cuda) device; '
-                             f'got {dev}.  There is no CPU fallback.')
-  if dev.index is None:
-    dev = torch.device('cuda', torch.cuda.current_device())
-  if not bufs_by_key or any(len(v) == 0 for v in bufs_by_key.values()):
-    raise ValueError('decode_png_batch: nothing to decode')
-  keys = list(bufs_by_key)
-  streams = [_as_stream(item) for k in keys for item in bufs_by_key[k]]
-  names = [(k, i) for k in keys for i in range(len(bufs_by_key[k]))]
+  dev = cuda_device(device, 'decode_png_batch', 'inflates and reconstructs')
+  out, rows = _plan(bufs_by_key, dev, lambda flat: [_as_stream(item) for item in flat])
+  streams = [p for _, _, p, _ in rows]
 
   L = _lib.lib()
-  n = len(streams)
+  n = len(rows)
   inflate_table = np.zeros((n, L.se3ds_png_inflate_fields()), np.int64)
   unfilter_table = np.zeros((n, L.se3ds_png_unfilter_fields()), np.int64)
   unfilter_at = inflate_table.nbytes               # the device buffer starts with the inflate table,
-  offset = (unfilter_at + unfilter_table.nbytes + 15) & ~15   # then the other, then the streams
-  out, idx, workspace_bytes = {}, 0, 0
-  for k in keys:
-    group = streams[idx:idx + len(bufs_by_key[k])]
-    p0 = group[0]
-    for p in group:
-      if p[:4] != p0[:4]:
-        raise ValueError(f'{k}: a {p.height}x{p.width} PNG of {p.channels} channels at bit depth '
-                         f'{p.bit_depth} in a batch of {p0.height}x{p0.width}, {p0.channels}, '
-                         f'{p0.bit_depth}')
-    shape = (len(group), p0.height, p0.width) + ((3,) if p0.channels == 3 else ())
-    out[k] = torch.empty(shape, dtype=torch.int16 if p0.bit_depth == 16 else torch.uint8, device=dev)
-    plane_bytes = p0.height * p0.row_bytes
-    inflated = p0.height * (1 + p0.row_bytes)
-    for i, p in enumerate(group):
-      inflate_table[idx + i] = (offset, len(p.compressed), workspace_bytes, inflated, 1 + p.row_bytes)
-      unfilter_table[idx + i] = (workspace_bytes, out[k].data_ptr() + i * plane_bytes, p.height,
-                                 p.row_bytes, p.bytes_per_pixel, int(p.bit_depth == 16))
-      offset += (len(p.compressed) + 15) & ~15
-      workspace_bytes += (inflated + 15) & ~15     # 16-byte aligned: the flush stores 16 bytes a lane
-    idx += len(group)
+  offsets, _ = layout([unfilter_at + unfilter_table.nbytes] +      # then the other, then the
+                      [len(p.compressed) for p in streams])        # streams
+  inflated = [p.height * (1 + p.row_bytes) for p in streams]
+  workspace_at, workspace_bytes = layout(inflated)   # 16-byte aligned: the flush stores 16 bytes a lane
+  for i, (_, _, p, to) in enumerate(rows):
+    inflate_table[i] = (offsets[1 + i], len(p.compressed), workspace_at[i], inflated[i], 1 + p.row_bytes)
+    unfilter_table[i] = (workspace_at[i], to, p.height, p.row_bytes, p.bytes_per_pixel,
+                         int(p.bit_depth == 16))
 
   with torch.cuda.device(dev):
-    staging = torch.empty((offset,), dtype=torch.uint8, pin_memory=True)
-    host = staging.numpy()
-    host[:unfilter_at] = inflate_table.reshape(-1).view(np.uint8)
-    host[unfilter_at:unfilter_at + unfilter_table.nbytes] = unfilter_table.reshape(-1).view(np.uint8)
-    for row, p in zip(inflate_table, streams):
-      host[row[0]:row[0] + row[1]] = np.frombuffer(p.compressed, np.uint8)
-    # as in the host path: copies and kernels are queued on the current stream, and the caching
-    # allocators (pinned and device) hand a freed block out again only behind that work
-    device_buf = staging.to(dev, non_blocking=True)
+    tables = np.concatenate([inflate_table.reshape(-1), unfilter_table.reshape(-1)])
+    device_buf, _ = upload([tables] + [p.compressed for p in streams], dev)
     workspace = torch.empty((workspace_bytes,), dtype=torch.uint8, device=dev)
     status = torch.empty((n,), dtype=torch.int32, device=dev)
-    rc = L.se3ds_png_inflate(_lib.ptr(device_buf), offset, _lib.ptr(workspace), workspace_bytes,
-                             inflate_table.ctypes.data, n, _lib.ptr(status), _lib.stream())
+    rc = L.se3ds_png_inflate(_lib.ptr(device_buf), device_buf.numel(), _lib.ptr(workspace),
+                             workspace_bytes, inflate_table.ctypes.data, n, _lib.ptr(status),
+                             _lib.stream())
     _lib.check(rc, 'se3ds_png_inflate')
     rc = L.se3ds_png_unfilter(_lib.ptr(workspace), workspace_bytes, _lib.ptr(device_buf) + unfilter_at,
                               unfilter_table.ctypes.data, n, _lib.stream())
     _lib.check(rc, 'se3ds_png_unfilter')
-    status_host = torch.empty((n,), dtype=torch.int32, pin_memory=True)
-    status_host.copy_(status, non_blocking=True)
-    event = torch.cuda.Event()
-    event.record()
-  return out, PendingDecode(event, status_host, names, streams)
+    return out, PendingDecode(status, [(k, i) for k, i, _, _ in rows], streams)
 
 
 # ------------------------------------------------------------------------------ encoding
@@ -458,36 +420,27 @@ def plane_geometry(x) -> Tuple[int, int, int]:
   return int(x.shape[0]), int(x.shape[1]) * int(x.shape[2]), int(x.shape[2])
 
 
-def encode_streams(images: Sequence[torch.Tensor], filters='adaptive', fill: int = None
-                   ) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
-  """The device half of encode_png_batch: -> (table, sizes, streams).  table: the descriptor table
-  (encode_table); sizes: uint32 (n, 2) = bytes of each image's deflate stream, Adler-32 of its
-  filtered bytes; streams: the downloaded compact buffer, image i's stream at table[i, 6].  fill:
-  the output buffer is set to this byte before the launches (tests look at what stays untouched).
-  A 16-bit plane -- (H,W,1) torch.int16 holding the bit patterns of uint16, the convention of
-  datasets.indoor_datasets.RAW_DTYPES, or torch.uint16 -- has 2 in field 3 of its row and sends the
-  whole batch through se3ds_png_encode_planes; a batch of uint8 images takes se3ds_png_encode."""
-  images = list(images)
-  _lib.require_cuda(*images)
-  dev = images[0].device
-  for x in images:
-    _check_pixels(x.shape, x.dtype, 'encode_png_batch')
-    if x.device != dev:
-      raise ValueError(f'encode_png_batch: a tensor on {x.device} in a batch on {dev}')
-  images = [x.contiguous() for x in images]
-  modes = _filter_modes(filters, len(images))
+def launch_encode(images: Sequence[torch.Tensor], modes: Sequence[int], fill: int = None
+                  ) -> Tuple[np.ndarray, torch.Tensor, int]:
+  """Queues the encode of contiguous (H,W,C) device tensors of one device on its current stream:
+  -> (table, result, head).  table: the descriptor table (encode_table); result: the uint8 device
+  buffer that will hold 8 bytes per image (uint32 bytes of its deflate stream, Adler-32 of its
+  filtered bytes) and, from `head` on, the compact streams, image i's at table[i, 6].  One upload
+  (the table) and the entry's two launches; nothing is waited for.  A 16-bit plane has 2 in field 3
+  of its row and sends the whole batch through se3ds_png_encode_planes; a batch of uint8 images
+  takes se3ds_png_encode.  fill: as encode_streams."""
   L = _lib.lib()
   n = len(images)
+  dev = images[0].device
   geometries = [plane_geometry(x) for x in images]
   table = encode_table([x.data_ptr() for x in images], geometries, modes)
   assert table.shape[1] == L.se3ds_png_encode_fields()
   entry = 'se3ds_png_encode_planes' if any(g[2] == 2 for g in geometries) else 'se3ds_png_encode'
   workspace_bytes = getattr(L, entry + '_workspace_bytes')(table.ctypes.data, n)
   out_bytes = getattr(L, entry + '_out_bytes')(table.ctypes.data, n)
-  head = (8 * n + 15) & ~15   # the sizes lead the download buffer
+  head = aligned(8 * n)   # the sizes lead the result buffer
   with torch.cuda.device(dev):
-    staging = torch.from_numpy(table.reshape(-1)).pin_memory()
-    table_dev = staging.to(dev, non_blocking=True)
+    table_dev, _ = upload([table], dev)
     workspace = torch.empty((max(workspace_bytes, 16),), dtype=torch.uint8, device=dev)
     result = torch.empty((head + out_bytes,), dtype=torch.uint8, device=dev)
     if fill is not None:
@@ -496,10 +449,29 @@ def encode_streams(images: Sequence[torch.Tensor], filters='adaptive', fill: int
                            workspace_bytes, _lib.ptr(result) + head, out_bytes, _lib.ptr(result), 3,
                            _lib.stream())
     _lib.check(rc, entry)
-    host = torch.empty((head + out_bytes,), dtype=torch.uint8, pin_memory=True)
-    host.copy_(result, non_blocking=True)
-    torch.cuda.current_stream().synchronize()
-  buf = host.numpy()
+  return table, result, head
+
+
+def encode_streams(images: Sequence[torch.Tensor], filters='adaptive', fill: int = None
+                   ) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+  """The device half of encode_png_batch: -> (table, sizes, streams).  table: the descriptor table
+  (encode_table); sizes: uint32 (n, 2) = bytes of each image's deflate stream, Adler-32 of its
+  filtered bytes; streams: the downloaded compact buffer, image i's stream at table[i, 6].  fill:
+  the output buffer is set to this byte before the launches (tests look at what stays untouched).
+  A 16-bit plane is (H,W,1) torch.int16 holding the bit patterns of uint16, the convention of
+  datasets.indoor_datasets.RAW_DTYPES, or torch.uint16.  launch_encode, one download of the whole
+  result, one synchronisation."""
+  images = list(images)
+  _lib.require_cuda(*images)
+  dev = images[0].device
+  for x in images:
+    _check_pixels(x.shape, x.dtype, 'encode_png_batch')
+    if x.device != dev:
+      raise ValueError(f'encode_png_batch: a tensor on {x.device} in a batch on {dev}')
+  images = [x.contiguous() for x in images]
+  n = len(images)
+  table, result, head = launch_encode(images, _filter_modes(filters, n), fill)
+  buf = Readback(result).wait()
   return table, buf[:8 * n].view(np.uint32).reshape(n, 2), buf[head:]
 
 

@@ -98,6 +98,39 @@ def test_rest_of_the_output_buffer_is_untouched_and_runs_are_identical(enc):
   assert np.array_equal(sizes, enc.sizes) and np.array_equal(buffer, enc.buffer)
 
 
+def _small_images():
+  """A 3x5 RGB and a 1x1 grey uint8 image and a 2x7 int16 plane."""
+  rng = np.random.default_rng(31)
+  rgb = torch.from_numpy(rng.integers(0, 256, (3, 5, 3), dtype=np.uint8)).to(DEV)
+  grey = torch.from_numpy(rng.integers(0, 256, (1, 1, 1), dtype=np.uint8)).to(DEV)
+  return rgb, grey, _as_int16(rng.integers(0, 65536, (2, 7), dtype=np.uint16))
+
+
+def test_launch_encode_and_a_download_equal_encode_streams():
+  images = list(_small_images())
+  want_table, want_sizes, want_streams = png.encode_streams(images, 'adaptive', fill=CANARY)
+  table, result, head = png.launch_encode(images, [png.ADAPTIVE] * 3, fill=CANARY)
+  buf = result.cpu().numpy()   # waits for the stream the encode is queued on
+  assert head == 32   # the 24 bytes of sizes, rounded up to 16
+  assert np.array_equal(table, want_table)
+  assert np.array_equal(buf[:8 * 3].view(np.uint32).reshape(3, 2), want_sizes)
+  assert np.array_equal(buf[head:], want_streams)
+  assert all(int(s) > 0 for s in want_sizes[:, 0])
+
+
+def test_a_uint8_batch_equals_its_images_encoded_one_by_one():
+  """A batch without a 16-bit plane takes se3ds_png_encode, as every image alone does."""
+  rgb, grey, _ = _small_images()
+  table, sizes, streams = png.encode_streams([rgb, grey], 'adaptive')
+  assert not np.any(table[:, 3] == 2)
+  for i, x in enumerate((rgb, grey)):
+    _, one_size, one = png.encode_streams([x], 'adaptive')
+    assert np.array_equal(sizes[i], one_size[0])
+    at, size = int(table[i, 6]), int(sizes[i, 0])
+    assert size > 0 and np.array_equal(streams[at:at + size], one[:size])
+  assert png.encode_png_batch([rgb, grey]) == png.encode_png_batch([rgb]) + png.encode_png_batch([grey])
+
+
 LENGTHS = (0, 1, 3, 15, 16, 17, 63, 64, 65, 4097, 70001)
 
 
