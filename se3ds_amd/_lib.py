@@ -1,7 +1,9 @@
-"""ctypes binding of libse3ds_hip.so (include/se3ds_hip.h).  There is NO fallback: if the
-library is missing or a GPU entry point fails, the caller gets an exception."""
+"""ctypes binding of libse3ds_hip.so, derived from include/se3ds_hip.h: the header is the only
+signature table and the only list of ABI constants.  There is NO fallback: if the library is
+missing or a GPU entry point fails, the caller gets an exception."""
 import ctypes
 import os
+import re
 
 import torch
 
@@ -10,125 +12,63 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # two builds on one box; they used to copy over the in-tree file and a killed job left the wrong one
 # behind -- ADVICE r5).  Unset: the in-tree build, the only one the tests and the bench ever load.
 SO_PATH = os.environ.get('SE3DS_LIB') or os.path.join(_HERE, 'csrc', 'libse3ds_hip.so')
-
-F32, I32, U8, BF16 = 0, 1, 2, 3
-_DTYPE_CODE = {torch.float32: F32, torch.int32: I32, torch.uint8: U8, torch.bfloat16: BF16}
+HEADER_PATH = os.path.join(_HERE, '..', 'include', 'se3ds_hip.h')
 
 c_int, c_i64, c_f, c_p, c_sz = (ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p,
                                 ctypes.c_size_t)
 c_d = ctypes.c_double
+_SCALARS = {'int': c_int, 'int64_t': c_i64, 'size_t': c_sz, 'float': c_f, 'double': c_d,
+            'uint32_t': ctypes.c_uint32}
+_DECL = re.compile(r'([\w\s*]+?)\b(se3ds_\w+)\s*\(([^()]*)\)')
+_INT = re.compile(r'\(?\s*(-?(?:0[xX][0-9a-fA-F]+|\d+))\s*\)?')
 
-# name -> (restype, argtypes); mirrors include/se3ds_hip.h one to one.
-_SIGS = {
-    'se3ds_version': (ctypes.c_char_p, []),
-    'se3ds_last_error': (ctypes.c_char_p, []),
-    'se3ds_unproject_equirect': (c_int, [c_p, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int,
-                                         c_int, c_int, c_f, c_f, c_p, c_p, c_p]),
-    'se3ds_unproject_equirect_into': (c_int, [c_p, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int,
-                                              c_int, c_int, c_f, c_f, c_p, c_p, c_i64, c_i64, c_p]),
-    'se3ds_splat_workspace_bytes': (c_sz, [c_int, c_i64, c_int, c_int, c_int]),
-    'se3ds_project_equirect': (c_int, [c_p, c_p, c_p, c_int, c_int, c_i64, c_int, c_int, c_int,
-                                       c_f, c_f, c_f, c_p, c_p, c_p, c_f, c_p, c_sz, c_p]),
-    'se3ds_project_equirect_memory': (c_int, [c_p, c_p, c_p, c_int, c_int, c_i64, c_i64, c_int, c_int,
-                                              c_int, c_f, c_f, c_f, c_p, c_p, c_p, c_f, c_p, c_sz, c_p]),
-    'se3ds_warp_views_to_target': (c_int, [c_p, c_int, c_p, c_p, c_int, c_int, c_int, c_int, c_int,
-                                           c_f, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_p,
-                                           c_int, c_int, c_f, c_p, c_p, c_p, c_f, c_p, c_sz, c_p]),
-    'se3ds_project_to_feat': (c_int, [c_p, c_p, c_int, c_int, c_i64, c_int, c_int, c_int, c_f, c_f,
-                                      c_f, c_p, c_p, c_p, c_f, c_p, c_sz, c_p]),
-    'se3ds_splat_debug_indices': (c_int, [c_p, c_int, c_i64, c_p, c_p, c_p]),
-    'se3ds_splat_promise_sticky': (c_int, [c_p, c_p, c_int, c_p]),
-    'se3ds_feats_byte_range': (c_int, [c_p, c_int, c_i64, c_f, c_p, c_p]),
-    'se3ds_splat_promise_broken': (c_int, [c_p, c_int, c_i64, c_p, c_p]),
-    'se3ds_debug_fast_fxy': (c_int, [c_p, c_i64, c_int, c_int, c_p, c_p, c_p, c_p]),
-    'se3ds_unproject_perspective': (c_int, [c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int,
-                                            c_f, c_p, c_p, c_p]),
-    'se3ds_interp_bilinear': (c_int, [c_p, c_p, c_int, c_int, c_int, c_int, c_i64, c_int, c_p,
-                                      c_p]),
-    'se3ds_rotate_coords': (c_int, [c_p, c_p, c_int, c_i64, c_int, c_int, c_p, c_p]),
-    'se3ds_perspective_coords': (c_int, [c_p, c_p, c_i64, c_int, c_f, c_p, c_p]),
-    'se3ds_persp_from_equirect_coords': (c_int, [c_p, c_p, c_int, c_int, c_int, c_int, c_p, c_p]),
-    'se3ds_input_transform': (c_int, [c_p] * 9 + [c_int] * 5 + [c_p] * 8),
-    'se3ds_video_transform': (c_int, [c_p] * 7 + [c_int] * 6 + [c_p] * 7),
-    'se3ds_png_unfilter': (c_int, [c_p, c_i64, c_p, c_p, c_int, c_p]),
-    'se3ds_png_unfilter_fields': (c_int, []),
-    'se3ds_png_unfilter_max_row_bytes': (c_int, []),
-    'se3ds_png_inflate': (c_int, [c_p, c_i64, c_p, c_i64, c_p, c_int, c_p, c_p]),
-    'se3ds_png_inflate_fields': (c_int, []),
-    'se3ds_png_inflate_ring_bytes': (c_int, []),
-    'se3ds_jpeg_decode': (c_int, [c_p, c_i64, c_p, c_i64, c_p, c_int, c_p, c_int, c_p, c_int, c_p]),
-    'se3ds_jpeg_decode_workspace_bytes': (c_sz, [c_p, c_int]),
-    'se3ds_jpeg_decode_fields': (c_int, []),
-    'se3ds_jpeg_decode_segment_fields': (c_int, []),
-    'se3ds_jpeg_decode_lanes': (c_int, []),
-    'se3ds_jpeg_decode_chunk_bytes': (c_int, []),
-    'se3ds_grid_quantize': (c_int, [c_p] + [c_int] * 8 + [c_p, c_p]),
-    'se3ds_png_encode': (c_int, [c_p, c_p, c_int, c_p, c_i64, c_p, c_i64, c_p, c_int, c_p]),
-    'se3ds_png_encode_workspace_bytes': (c_sz, [c_p, c_int]),
-    'se3ds_png_encode_out_bytes': (c_i64, [c_p, c_int]),
-    'se3ds_png_encode_fields': (c_int, []),
-    'se3ds_png_encode_max_row_bytes': (c_int, []),
-    'se3ds_adler32_combine': (ctypes.c_uint32, [ctypes.c_uint32, ctypes.c_uint32, c_i64]),
-    'se3ds_png_encode_planes': (c_int, [c_p, c_p, c_int, c_p, c_i64, c_p, c_i64, c_p, c_int, c_p]),
-    'se3ds_png_encode_planes_workspace_bytes': (c_sz, [c_p, c_int]),
-    'se3ds_png_encode_planes_out_bytes': (c_i64, [c_p, c_int]),
-    'se3ds_record_planes': (c_int, [c_p, c_p, c_p, c_i64, c_p, c_p, c_p, c_p]),
-    'se3ds_assemble_segments': (c_int, [c_p, c_int, c_p, c_p, c_int, c_p, c_i64, c_p]),
-    'se3ds_assemble_fields': (c_int, []),
-    'se3ds_assemble_max_segment_bytes': (c_i64, []),
-    'se3ds_patch_crc': (c_int, [c_p, c_int, c_p, c_p, c_int, c_p, c_i64, c_p]),
-    'se3ds_patch_crc_fields': (c_int, []),
-    'se3ds_crc32c_multi': (c_int, [c_p, c_i64, c_p, c_p, c_int, c_p, c_p, c_sz, c_p]),
-    'se3ds_crc32c_workspace_bytes': (c_sz, [c_i64, c_int]),
-    'se3ds_crc32c_fields': (c_int, []),
-    'se3ds_crc32c_block_bytes': (c_int, []),
-    'se3ds_crc32z_multi': (c_int, [c_p, c_i64, c_p, c_p, c_int, c_p, c_p, c_sz, c_p]),
-    'se3ds_crc32z_workspace_bytes': (c_sz, [c_i64, c_int]),
-    'se3ds_crc32z_fields': (c_int, []),
-    'se3ds_crc32z_block_bytes': (c_int, []),
-    'se3ds_collision_count': (c_int, [c_p, c_int, c_int, c_int, c_p, c_p, c_p, c_f, c_int, c_p, c_p]),
-    'se3ds_collision_check_windows': (c_int, [c_p, c_p, c_int, c_int, c_int, c_int]),
-    'se3ds_perspective_to_pointcloud': (c_int, [c_p, c_p, c_int, c_int, c_int, c_p, c_p, c_int, c_f, c_p, c_p,
-                                                c_p, c_p, c_p, c_int, c_int, c_f, c_f, c_p, c_p, c_p]),
-    'se3ds_perspective_guidance': (c_int, [c_p, c_p, c_int, c_int, c_p, c_p, c_int, c_int, c_p, c_p, c_p,
-                                           c_p]),
-    'se3ds_mask_pano': (c_int, [c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_f, c_p, c_p]),
-    'se3ds_resize': (c_int, [c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_p, c_p]),
-    'se3ds_mean_f32': (c_int, [c_p, c_i64, c_p, c_p]),
-    'se3ds_compact_workspace_bytes': (c_sz, [c_i64]),
-    'se3ds_compact_valid': (c_int, [c_p, c_p, c_int, c_int, c_i64, c_int, c_f, c_p, c_p, c_p, c_p,
-                                    c_sz, c_p]),
-    'se3ds_inception_preprocess': (c_int, [c_p, c_int, c_int, c_int, c_p, c_int, c_int, c_int, c_p,
-                                           c_int, c_p]),
-    'se3ds_inception_maxpool3s2': (c_int, [c_p] + [c_int] * 5 + [c_p, c_int, c_int, c_p]),
-    'se3ds_inception_avgpool3s1': (c_int, [c_p] + [c_int] * 5 + [c_p, c_int, c_int, c_p]),
-    'se3ds_global_avg_pool': (c_int, [c_p, c_int, c_int, c_int, c_int, c_p, c_p]),
-    'se3ds_softmax_rows': (c_int, [c_p, c_int, c_i64, c_int, c_p, c_p]),
-    'se3ds_feature_moments_accumulate': (c_int, [c_p, c_i64, c_int, c_p, c_p, c_p, c_p]),
-    'se3ds_f64_gemm': (c_int, [c_p, c_p, c_p, c_int, c_d, c_d, c_p]),
-    'se3ds_moments_mean_cov': (c_int, [c_p, c_p, c_p, c_int, c_p, c_p, c_p]),
-    'se3ds_sqrt_trace_workspace_bytes': (c_sz, [c_int]),
-    'se3ds_sqrt_trace': (c_int, [c_p, c_int, c_int, c_d, c_p, c_p, c_sz, c_p, c_p]),
-    'se3ds_frechet_terms': (c_int, [c_p, c_p, c_p, c_p, c_int, c_p, c_p]),
-    'se3ds_nn_inpaint': (c_int, [c_p, c_int, ctypes.c_uint32, c_int, c_int, c_int, c_p, c_p, c_p, c_sz,
-                                 c_int, c_p]),
-    'se3ds_nn_inpaint_workspace_bytes': (c_sz, [c_int, c_int, c_int]),
-    'se3ds_nn_inpaint_row_segment': (c_int, []),
-    'se3ds_nn_inpaint_col_tile_rows': (c_int, []),
-    'se3ds_seq_iou_sums': (c_int, [c_p, c_p, c_p, c_i64, c_i64, c_int, c_p, c_p, c_sz, c_p]),
-    'se3ds_seq_label_match': (c_int, [c_p, c_p, c_int, c_p, c_int, c_i64, c_i64, c_p, c_p, c_sz, c_p]),
-    'se3ds_seq_sums_workspace_bytes': (c_sz, [c_i64, c_i64]),
-    'se3ds_seq_sums_chunk': (c_int, []),
-    'se3ds_seq_finalize': (c_int, [c_p, c_p, c_int, c_int, c_int, c_p, c_p, c_p]),
-    'se3ds_cmap_to_label': (c_int, [c_p, c_int, c_i64, c_p, c_int, c_p, c_p]),
-    'se3ds_label_to_color': (c_int, [c_p, c_int, c_i64, c_p, c_int, c_p, c_p]),
-    'se3ds_ply_ascii': (c_int, [c_p, c_i64, c_p, c_int, c_i64, c_p, c_i64, c_p, c_p, c_sz, c_int, c_p]),
-    'se3ds_ply_ascii_workspace_bytes': (c_sz, [c_i64]),
-    'se3ds_ply_chunk_points': (c_int, []),
-    'se3ds_ply_max_line_bytes': (c_int, []),
-    'se3ds_ply_max_points': (c_i64, []),
-    'se3ds_ply_binary': (c_int, [c_p, c_i64, c_p, c_int, c_i64, c_p, c_i64, c_p, c_p]),
-}
+
+def _ctype(decl, name, is_param):
+  """ctypes class of one parameter (type and optional name) or of a return type."""
+  words = [w for w in decl.split() if w != 'const']
+  if re.fullmatch(r'[\w\s*]+', decl):   # no array, function-pointer or variadic declarator
+    if is_param and '*' in decl:
+      return c_p
+    if not is_param and ''.join(words) == 'char*':
+      return ctypes.c_char_p
+    if 1 <= len(words) <= 1 + is_param and words[0] in _SCALARS:
+      return _SCALARS[words[0]]
+  raise ValueError(f'include/se3ds_hip.h: {name}: no ctypes rule for `{decl}`')
+
+
+def parse_header(text):
+  """(signatures, constants) of a header in the style of include/se3ds_hip.h: name -> (restype,
+  argtypes) for every `<ret> se3ds_<name>(<params>);` and SE3DS_<NAME> -> int for every integer
+  #define.  A pointer parameter is c_void_p, a scalar its ctypes twin, `const char*` returns
+  c_char_p; anything the rules do not cover is a ValueError, never a skipped line."""
+  text = re.sub(r'/\*.*?\*/|//[^\n]*', ' ', text, flags=re.S)
+  abi = {}
+  for name, value in re.findall(r'^[ \t]*#[ \t]*define[ \t]+(SE3DS_\w+)[ \t]+(\S.*?)[ \t]*$', text, re.M):
+    m = _INT.fullmatch(value)
+    if not m:
+      raise ValueError(f'include/se3ds_hip.h: #define {name}: `{value}` is not an integer literal')
+    abi[name] = int(m.group(1), 0)
+  text = re.sub(r'^[ \t]*#.*$|extern\s+"C"\s*\{', ' ', text, flags=re.M)
+  sigs = {}
+  for stmt in text.split(';'):
+    named = re.search(r'\bse3ds_\w+(?=\s*\()', stmt)
+    if not named:
+      continue
+    name, m = named.group(0), _DECL.fullmatch(' '.join(stmt.split()))
+    if not m or m.group(2) != name:
+      raise ValueError(f'include/se3ds_hip.h: {name}: not a plain `<ret> {name}(<params>);` declaration')
+    params = m.group(3).strip()
+    args = [] if params == 'void' else [_ctype(p.strip(), name, True) for p in params.split(',')]
+    sigs[name] = (_ctype(m.group(1).strip(), name, False), args)
+  return sigs, abi
+
+
+with open(HEADER_PATH) as _f:
+  _SIGS, ABI = parse_header(_f.read())   # name -> (restype, argtypes); SE3DS_<NAME> -> int
+
+F32, I32, U8, BF16 = ABI['SE3DS_F32'], ABI['SE3DS_I32'], ABI['SE3DS_U8'], ABI['SE3DS_BF16']
+_DTYPE_CODE = {torch.float32: F32, torch.int32: I32, torch.uint8: U8, torch.bfloat16: BF16}
+_ERROR_NAMES = {v: k for k, v in ABI.items() if k.startswith('SE3DS_E_')}
 
 _lib = None
 
@@ -141,20 +81,6 @@ def declared_symbols():
   return sorted(_SIGS)
 
 
-def register(sigs):
-  """Lets other binding modules (conv, norm, ...) add their signatures before load."""
-  _SIGS.update(sigs)
-  if _lib is not None:
-    _bind(_lib, sigs)
-
-
-def _bind(lib, sigs):
-  for name, (res, args) in sigs.items():
-    fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
-    fn.restype = res
-    fn.argtypes = args
-
-
 def lib():
   global _lib
   if _lib is None:
@@ -163,7 +89,10 @@ def lib():
           f'{SO_PATH} not found: build it with `python -m se3ds_amd.csrc.build` '
           '(__graft_entry__.build()).  There is no CPU fallback for the SE3DS hot path.')
     l = ctypes.CDLL(SO_PATH)
-    _bind(l, _SIGS)
+    for name, (res, args) in _SIGS.items():
+      fn = getattr(l, name)  # AttributeError if the .so lacks a declared symbol
+      fn.restype = res
+      fn.argtypes = args
     _lib = l
   return _lib
 
@@ -193,5 +122,4 @@ def require_cuda(*tensors):
 def check(rc, what):
   if rc != 0:
     msg = lib().se3ds_last_error().decode()
-    names = {-1: 'BADSHAPE', -2: 'BADDTYPE', -3: 'WORKSPACE', -4: 'LAUNCH', -5: 'UNSUPPORTED'}
-    raise Se3dsHipError(f'{what} failed: SE3DS_E_{names.get(rc, rc)} {msg}')
+    raise Se3dsHipError(f'{what} failed: {_ERROR_NAMES.get(rc, f"SE3DS_E_{rc}")} {msg}')

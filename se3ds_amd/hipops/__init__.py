@@ -1,102 +1,3 @@
-"""Host-side wrappers of the libse3ds_hip.so network kernels: ctypes signatures, a small
-reverse-mode tape (gradient accumulation runs in our own kernels, not in torch) and the
-differentiable ops the SE3DS layers are written with."""
-import ctypes
-
-from se3ds_amd import _lib
-from se3ds_amd._lib import c_int, c_i64, c_f, c_p, c_sz
-
-_lib.register({
-    'se3ds_weight_prep': (c_int, [c_p, c_i64, c_int, c_int, c_p, c_p, c_p]),
-    'se3ds_weight_prep_multi': (c_int, [c_p, c_int, c_i64, c_p]),
-    'se3ds_conv2d_fwd': (c_int, [c_p, c_p, c_p, c_int] + [c_int] * 13 + [c_p, c_int, c_p, c_p, c_p,
-                                                                      c_p, c_int, c_f, c_p]),
-    'se3ds_conv2d_fwd_stats': (c_int, [c_p, c_p, c_p, c_int] + [c_int] * 13 + [c_p, c_int, c_p, c_p,
-                                                                            c_p, c_p, c_int, c_f, c_p,
-                                                                            c_p]),
-    'se3ds_conv2d_fwd_stats_rows': (c_i64, [c_int] * 11),
-    'se3ds_conv_transpose2x2_fwd': (c_int, [c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_p, c_p]),
-    'se3ds_conv2d_dgrad': (c_int, [c_p, c_p, c_p, c_int] + [c_int] * 13 + [c_p, c_p, c_p, c_p,
-                                                                        c_int, c_f, c_p]),
-    'se3ds_conv2d_dgrad_acc': (c_int, [c_p, c_p, c_p, c_int] + [c_int] * 13 + [c_p, c_p, c_p, c_p,
-                                                                        c_int, c_f, c_p, c_p]),
-    'se3ds_conv2d_dgrad_bnstats_rows': (c_i64, [c_int] * 10),
-    'se3ds_conv2d_dgrad_bnstats': (c_int, [c_p, c_p, c_p, c_int] + [c_int] * 13 +
-                                   [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_f, c_p, c_p]),
-    'se3ds_conv2d_wgrad_workspace_bytes': (c_sz, [c_int] * 7),
-    'se3ds_conv2d_wgrad': (c_int, [c_p, c_p, c_p, c_int] + [c_int] * 13 + [c_p, c_int, c_p, c_p, c_int,
-                                                                        c_p, c_sz, c_p]),
-    'se3ds_conv2d_wgrad_partial': (c_int, [c_p, c_p, c_p, c_int] + [c_int] * 13 + [c_p, c_int, c_p, c_p,
-                                                                                c_sz, c_p, c_p]),
-    'se3ds_wgrad_reduce_multi': (c_int, [c_p, c_int, c_i64, c_p]),
-    'se3ds_wgrad_reduce_tile': (c_int, []),
-    'se3ds_fastdiv_host': (ctypes.c_uint32, [ctypes.c_uint32, ctypes.c_uint32]),
-    'se3ds_debug_last_conv_route': (c_int, []),
-    'se3ds_debug_conv_route_history': (c_int, [c_int]),
-    'se3ds_debug_conv_route_name': (ctypes.c_char_p, [c_int]),
-    'se3ds_conv2d_wgrad_swapped_workspace_bytes': (c_sz, [c_int] * 6),
-    'se3ds_conv2d_wgrad_swapped': (c_int, [c_p, c_p, c_p, c_int] + [c_int] * 8 + [c_p, c_sz, c_p]),
-    'se3ds_mask_window': (c_int, [c_p] + [c_int] * 11 + [c_p, c_p, c_p, c_p, c_p]),
-    'se3ds_norm_workspace_bytes': (c_sz, [c_int, c_int]),
-    'se3ds_norm_stats': (c_int, [c_p, c_int, c_int, c_i64, c_int, c_p, c_p, c_p, c_p, c_sz, c_p]),
-    'se3ds_norm_reduce_rows': (c_int, [c_p, c_i64, c_int, c_p, c_p, c_sz, c_p]),
-    'se3ds_norm_reduce_rows_dst': (c_int, [c_p, c_i64, c_int, c_p, c_p, c_p, c_p, c_sz, c_p]),
-    'se3ds_colsum_row_scale': (c_int, [c_p, c_int, c_i64, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
-    'se3ds_norm_reduce_rows_finalize': (c_int, [c_p, c_i64, c_int, c_f, c_p, c_p, c_f, c_f, c_p, c_p, c_p,
-                                                c_p, c_p, c_p, c_p]),
-    'se3ds_norm_finalize': (c_int, [c_p, c_f, c_int, c_int, c_p, c_p, c_f, c_f, c_p, c_p, c_int,
-                                    c_p, c_p, c_p, c_p, c_p]),
-    'se3ds_norm_apply': (c_int, [c_p, c_int, c_int, c_i64, c_int, c_p, c_p, c_p, c_p, c_int, c_f,
-                                 c_p, c_p, c_p]),
-    'se3ds_norm_bwd_stats': (c_int, [c_p, c_p, c_p, c_int, c_int, c_i64, c_int, c_p, c_p, c_int,
-                                     c_f, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
-    'se3ds_norm_bwd_apply': (c_int, [c_p, c_p, c_p, c_int, c_int, c_i64, c_int, c_p, c_p, c_p, c_p,
-                                     c_f, c_int, c_f, c_p, c_p, c_p, c_int, c_f, c_p]),
-    'se3ds_norm_bwd_cg_supported': (c_int, [c_int, c_i64, c_int, c_int, c_int, c_int]),
-    'se3ds_norm_bwd_cg_workspace_bytes': (c_sz, [c_int]),
-    'se3ds_norm_bwd_cg_col_rows': (c_int, [c_i64, c_int]),
-    'se3ds_norm_bwd_cg': (c_int, [c_p, c_p, c_int, c_i64, c_int, c_p, c_p, c_p, c_f, c_int, c_f, c_p,
-                                  c_p, c_p, c_int, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
-    'se3ds_norm_bwd_apply_rows': (c_int, [c_p, c_p, c_int, c_i64, c_int, c_p, c_p, c_p, c_p, c_f,
-                                          c_int, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
-    'se3ds_affine_bwd': (c_int, [c_p, c_p, c_int, c_int, c_i64, c_int, c_p, c_int, c_f, c_p, c_p,
-                                 c_p, c_p]),
-    'se3ds_act_bwd': (c_int, [c_p, c_p, c_int, c_i64, c_int, c_f, c_p, c_p]),
-    'se3ds_add': (c_int, [c_p, c_p, c_int, c_i64, c_p, c_p]),
-    'se3ds_row_scale': (c_int, [c_p, c_int, c_i64, c_int, c_p, c_p, c_p]),
-    'se3ds_maxpool2x2_fwd': (c_int, [c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_p]),
-    'se3ds_maxpool2x2_bwd': (c_int, [c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_p]),
-    'se3ds_avgpool3s2_fwd': (c_int, [c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_p]),
-    'se3ds_avgpool3s2_bwd': (c_int, [c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_p]),
-    'se3ds_upsample2x_fwd': (c_int, [c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_p]),
-    'se3ds_upsample2x_bwd': (c_int, [c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_p]),
-    'se3ds_copy_channels': (c_int, [c_p, c_int, c_int, c_int, c_p, c_int, c_int, c_int, c_int,
-                                    c_i64, c_p]),
-    'se3ds_fill': (c_int, [c_p, c_int, c_i64, c_f, c_p]),
-    'se3ds_head_fwd': (c_int, [c_p, c_int, c_i64, c_int, c_p, c_p]),
-    'se3ds_head_bwd': (c_int, [c_p, c_p, c_p, c_int, c_i64, c_int, c_p, c_p]),
-    'se3ds_sample_sum': (c_int, [c_p, c_p, c_p, c_int, c_i64, c_int, c_int, c_p, c_p, c_p]),
-    'se3ds_l1_grad': (c_int, [c_p, c_p, c_p, c_p, c_p, c_int, c_i64, c_int, c_int, c_p, c_p]),
-    'se3ds_recip_clamp': (c_int, [c_p, c_int, c_f, c_p, c_p]),
-    'se3ds_hinge': (c_int, [c_p, c_int, c_i64, c_f, c_f, c_p, c_p, c_p, c_p]),
-    'se3ds_multi_sqnorm': (c_int, [c_p, c_p, c_i64, c_p, c_int, c_p, c_p, c_p]),
-    'se3ds_multi_clip_by_norm': (c_int, [c_p, c_p, c_i64, c_p, c_int, c_f, c_p, c_p]),
-    'se3ds_mean_clipped_norm': (c_int, [c_p, c_int, c_f, c_p, c_p]),
-    'se3ds_multi_adam_keras': (c_int, [c_p, c_p, c_p, c_p, c_i64, c_f, c_f, c_f, c_f, c_i64, c_p]),
-    'se3ds_multi_adam_keras_ema': (c_int, [c_p, c_p, c_p, c_p, c_i64, c_f, c_f, c_f, c_f, c_i64, c_p,
-                                           c_f, c_p]),
-    'se3ds_multi_clip_adam_keras_ema': (c_int, [c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_f, c_p, c_f, c_f,
-                                                c_f, c_f, c_i64, c_p, c_f, c_p]),
-    'se3ds_multi_ema': (c_int, [c_p, c_p, c_i64, c_f, c_p]),
-    'se3ds_spectral_table_fields': (c_int, []),
-    'se3ds_spectral_part_rows': (c_int, []),
-    'se3ds_spectral_vpart_len': (c_int, []),
-    'se3ds_spectral_power_iter': (c_int, [c_p, c_int, c_int, c_p]),
-    'se3ds_spectral_bwd_fixup': (c_int, [c_p, c_int, c_p]),
-    'se3ds_spectral_bwd_dots': (c_int, [c_p, c_int, c_p]),
-    'se3ds_multi_sqnorm_sn': (c_int, [c_p, c_p, c_i64, c_p, c_int, c_p, c_p, c_p, c_int, c_p]),
-    'se3ds_multi_clip_by_norm_sn': (c_int, [c_p, c_p, c_i64, c_p, c_int, c_f, c_p, c_p, c_p]),
-    'se3ds_quantize': (c_int, [c_p, c_int, c_i64, c_int, c_f, c_f, c_f, c_f, c_f, c_f, c_p, c_int, c_p]),
-    'se3ds_pad2d': (c_int, [c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_f, c_p,
-                            c_p]),
-})
+"""Host-side wrappers of the libse3ds_hip.so network kernels: a small reverse-mode tape
+(gradient accumulation runs in our own kernels, not in torch) and the differentiable ops the
+SE3DS layers are written with."""

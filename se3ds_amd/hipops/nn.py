@@ -16,7 +16,6 @@ import torch
 import torch.distributed as dist
 
 from se3ds_amd import _lib
-from se3ds_amd import hipops  # noqa: F401  (registers the ctypes signatures)
 
 ACT_NONE, ACT_RELU, ACT_LRELU = 0, 1, 2
 BN_EPS, BN_MOMENTUM = 1e-3, 0.99   # Keras SyncBatchNormalization defaults

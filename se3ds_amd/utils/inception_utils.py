@@ -40,7 +40,6 @@ import torch
 
 from se3ds_amd import _lib
 from se3ds_amd import gin_lite as gin
-from se3ds_amd import hipops  # noqa: F401  (registers the conv / copy signatures)
 from se3ds_amd.utils import pano_utils
 from se3ds_amd.utils import tf_bundle
 from se3ds_amd.utils.tf_checkpoint_keys import SUFFIX
@@ -580,7 +579,8 @@ def calculate_inception_score(pred, num_splits=10):
   return np.mean(scores), np.std(scores)
 
 # ------------------------------------------------------------------------------ device Frechet distance
-SQRT_CONVERGED, SQRT_CAP_REACHED, SQRT_NONFINITE = 0, 1, 2   # SE3DS_SQRT_* of include/se3ds_hip.h
+SQRT_CONVERGED, SQRT_CAP_REACHED, SQRT_NONFINITE = (
+    _lib.ABI['SE3DS_SQRT_CONVERGED'], _lib.ABI['SE3DS_SQRT_CAP_REACHED'], _lib.ABI['SE3DS_SQRT_NONFINITE'])
 FRECHET_METHODS = ('host', 'device')
 
 

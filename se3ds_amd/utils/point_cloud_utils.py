@@ -74,8 +74,8 @@ def _workspace(nbytes: int, device) -> torch.Tensor:
   return ws
 
 
-FEAT_BYTE_RANGE = 0x100   # include/se3ds_hip.h SE3DS_FEAT_BYTE_RANGE
-XYZ1_ONES_PRESET = 0x200  # include/se3ds_hip.h SE3DS_XYZ1_ONES_PRESET
+FEAT_BYTE_RANGE = _lib.ABI['SE3DS_FEAT_BYTE_RANGE']
+XYZ1_ONES_PRESET = _lib.ABI['SE3DS_XYZ1_ONES_PRESET']
 # A broken byte-range promise makes the packed splat pack f & 255: silently wrong features.  The
 # kernels raise a sticky flag in the workspace; it is read back ASYNCHRONOUSLY after the FIRST
 # promised splat of a process and after every _PROMISE_POLL_EVERY-th (a 1-thread kernel + a 4-byte

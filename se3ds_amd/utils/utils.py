@@ -29,7 +29,8 @@ MAX_COLOURS = 256
 _INPAINT_DTYPES = (torch.uint8, torch.int32, torch.float32)
 _LABEL_DTYPES = (torch.uint8, torch.int32)
 _SPATIAL_DTYPES = (torch.bool, torch.uint8, torch.int32, torch.float32)
-_SEQ_IOU, _SEQ_ACCURACY, _SEQ_IOU_LABELS = 0, 1, 2   # SE3DS_SEQ_* of include/se3ds_hip.h
+_SEQ_IOU, _SEQ_ACCURACY, _SEQ_IOU_LABELS = (
+    _lib.ABI['SE3DS_SEQ_IOU'], _lib.ABI['SE3DS_SEQ_ACCURACY'], _lib.ABI['SE3DS_SEQ_IOU_LABELS'])
 
 _workspaces = {}   # (purpose, device index, stream) -> uint8 tensor
 _cmaps = {}        # (device index, bytes of the int32 table) -> device int32 (K, 3)
