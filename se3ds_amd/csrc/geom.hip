@@ -14,6 +14,7 @@
 
 #include "common.h"
 #include "../../include/se3ds_geom_math.h"
+#include "splat_layout.h"
 
 namespace se3ds {
 namespace {
@@ -196,12 +197,8 @@ unproject_perspective_kernel(const int32_t* __restrict__ feats, const float* __r
 }
 
 // ------------------------------------------------------------------------------ splat
-// Workspace layout (bytes): [0,256) header: u32 sink_z (ordered), u32 sink_feat[C<=60];
-//   u32 zpart[kMaxSinkBlocks], u32 fpart[kMaxSinkBlocks][C] (per-block sink partials: the
-//   reference's sink pixel collects EVERY invalid point, and one atomic per wave on a single
-//   address serialises at ~12 ns each -- 200-600 us at 4 M points; per-block partials plus a
-//   one-block reduce cost ~3 us);  then int32 idx[N*M], float z[N*M].
-constexpr int kMaxSinkBlocks = 2048;
+// The workspace of every route is described once, in splat_layout.h: header and sink partials,
+// idx[N*M], z[N*M], then the arrays of the route the call takes.
 // Word 3 of the header (bytes 12..15, between sink_z and the sink features) is STICKY: the
 // packed / sorted splats OR a 1 into it when an int32 feature breaks the caller's
 // SE3DS_FEAT_BYTE_RANGE promise and nothing in the library ever clears it -- the owner of the
@@ -220,30 +217,6 @@ constexpr uint32_t kEpochTag = 0xA5000000u, kEpochTagMask = 0xff000000u;
 inline uint32_t next_splat_epoch() {
   static std::atomic<uint32_t> epoch{0};
   return kEpochTag | (++epoch & ~kEpochTagMask);
-}
-struct SplatWs {
-  uint32_t* sink_z;
-  uint32_t* sink_feat;
-  uint32_t* zpart;
-  uint32_t* fpart;
-  int32_t* idx;
-  float* z;
-};
-constexpr int kMaxSplatChannels = 60;
-__host__ __device__ inline size_t splat_hdr_bytes() {
-  return 256 + sizeof(uint32_t) * (size_t)kMaxSinkBlocks * (size_t)(1 + kMaxSplatChannels);
-}
-__host__ __device__ inline SplatWs carve_ws(void* ws, int n, int64_t m) {
-  SplatWs w;
-  char* p = (char*)ws;
-  w.sink_z = (uint32_t*)p;
-  w.sink_feat = (uint32_t*)(p + 16);
-  w.zpart = (uint32_t*)(p + 256);
-  w.fpart = w.zpart + kMaxSinkBlocks;
-  char* q = p + splat_hdr_bytes();
-  w.idx = (int32_t*)q;
-  w.z = (float*)(q + sizeof(int32_t) * (size_t)n * (size_t)m);
-  return w;
 }
 // grid for the per-point kernels: at most kMaxSinkBlocks blocks over (x, batch)
 inline dim3 point_grid(int64_t m, int n, int block) {
@@ -603,88 +576,28 @@ splat_debug_copy_kernel(SplatWs ws, int64_t total, int32_t* idx_out, float* z_ou
 // workgroup per tile resolves z-min and the per-channel max in LDS and writes depth, features
 // and mask directly.  min / max do not depend on the record order, so the result is bit-identical
 // to the scatter version.  Used for <= 7 channels and <= 4096 tiles per image.
-constexpr int kTileY = 16, kTileX = 128, kTilePx = kTileY * kTileX;
-constexpr int kMaxTiles = 4096;      // per image (LDS histogram)
-constexpr int kMaxBinChannels = 7;
-// The points of one image are cut into contiguous CHUNKS (one workgroup each, the same cut in the
-// count and the scatter pass).  Each chunk owns a histogram row, so record positions come from a
-// column scan of those rows: no global atomics anywhere (2 M cursor atomics cost ~70 us before).
-constexpr int kChunkThreads = 512;
-constexpr int kChunkPoints = 8192;   // minimum points per chunk (16 per thread)
-constexpr int kMaxChunks = 1024;     // per image
+// (tiles, chunks of points and the workspace arrays: splat_layout.h)
 constexpr int kScanWaves = 16;
 constexpr int kExactQueue = 2048;   // per chunk, points waiting for the binary64 path
 
-struct ChunkGeom {
-  int chunks;     // per image
-  int64_t per;    // points per chunk (multiple of kChunkThreads)
-};
-__host__ __device__ inline ChunkGeom chunk_geom(int64_t m, int n) {
-  int64_t cap = kMaxSinkBlocks / (n > 0 ? n : 1);
-  cap = cap < 1 ? 1 : (cap > kMaxChunks ? kMaxChunks : cap);
-  int64_t chunks = (m + kChunkPoints - 1) / kChunkPoints;
-  chunks = chunks < 1 ? 1 : (chunks > cap ? cap : chunks);
-  int64_t per = (m + chunks - 1) / chunks;
-  per = (per + kChunkThreads - 1) / kChunkThreads * kChunkThreads;
-  if (per < kChunkThreads) per = kChunkThreads;
-  chunks = (m + per - 1) / per;
-  ChunkGeom g;
-  g.chunks = (int)(chunks < 1 ? 1 : chunks);
-  g.per = per;
-  return g;
-}
-
-constexpr uint32_t kSliceRecords = 8192;   // records per band workgroup aimed at
 __host__ __device__ inline int tile_bands_log2(uint32_t count, uint32_t slice_records) {
   int lg = 0;
   while (lg < 3 && ((uint64_t)slice_records << lg) < count) ++lg;
   return lg;
 }
-// upper bound of the resolve items: every tile has one band, and a tile with c > slice_records
-// records has a power of two < 2 c / slice_records + 1 < 3 c / slice_records of them
-__host__ __device__ inline int64_t resolve_items_max(int64_t nb, int64_t points, uint32_t slice_records) {
-  return nb + 3 * ((points + slice_records - 1) / slice_records);
-}
-// (SE3DS_SPLAT_SLICE overrides the slice size: the parity tests use small slices to exercise
-// banded tiles on small images)
-inline uint32_t slice_records() {
-  static const uint32_t v = [] {
+// SE3DS_SPLAT_SLICE overrides the slice size of the binned (default kSliceRecords) and the packed
+// (kPSlice) resolve: the parity tests use small slices to exercise banded tiles on small images
+inline uint32_t slice_records(uint32_t dflt) {
+  static const long forced = [] {
     const char* e = getenv("SE3DS_SPLAT_SLICE");
-    const long x = e ? atol(e) : 0;
-    return (uint32_t)(x >= 16 ? x : (long)kSliceRecords);
+    return e ? atol(e) : 0;
   }();
-  return v;
+  return (uint32_t)(forced >= 16 ? forced : (long)dflt);
 }
-
-struct BinWs {
-  uint32_t* tile_count;   // [nb]
-  uint32_t* hist;         // [n][chunks][ntiles]: counts, then exclusive prefix over the chunks
-  uint32_t* fpart2;       // [items][C] sink partials of the occluded points, per resolve item
-  uint32_t* rec;          // [N*M][2 + C]: pixel inside the tile, z bits, feature bits
-};
-__host__ __device__ inline size_t align16(size_t v) { return (v + 15) / 16 * 16; }
-inline size_t bin_ws_bytes(int n, int64_t m, int height, int width, int channels) {
-  const size_t ntiles = (size_t)ceil_div(height, kTileY) * ceil_div(width, kTileX);
-  const size_t nb = (size_t)n * ntiles;
-  const size_t pts = (size_t)n * (size_t)(m > 0 ? m : 0);
-  const size_t chunks = (size_t)chunk_geom(m, n).chunks;
-  const size_t items = (size_t)resolve_items_max((int64_t)nb, (int64_t)pts, slice_records());
-  return align16(4 * nb) + align16(4 * nb * chunks) +
-         align16(4 * items * channels) + align16(4 * pts * (2 + channels));
-}
-inline BinWs carve_bin_ws(void* base, int n, int64_t m, int height, int width, int channels) {
-  const size_t ntiles = (size_t)ceil_div(height, kTileY) * ceil_div(width, kTileX);
-  const size_t nb = (size_t)n * ntiles;
-  const size_t chunks = (size_t)chunk_geom(m, n).chunks;
-  const size_t items = (size_t)resolve_items_max(
-      (int64_t)nb, (int64_t)n * (m > 0 ? m : 0), slice_records());
-  char* p = (char*)base;
-  BinWs w;
-  w.tile_count = (uint32_t*)p; p += align16(4 * nb);
-  w.hist = (uint32_t*)p; p += align16(4 * nb * chunks);
-  w.fpart2 = (uint32_t*)p; p += align16(4 * items * channels);
-  w.rec = (uint32_t*)p;
-  return w;
+// (read per call: the parity tests switch the (idx, z) tap on for single calls)
+inline bool splat_debug_tap() {
+  const char* e = getenv("SE3DS_SPLAT_DEBUG");
+  return e && atoi(e) != 0;
 }
 
 // packed target of a valid point: tile << 11 | pixel inside the tile (kTilePx = 2048).
@@ -1235,13 +1148,14 @@ int launch_splat_binned(const float* coords, const float* offset, const T* feats
                         int channels, int height, int width, float depth_scale, float input_void,
                         float output_void, float* depth, float* feat, float* mask, float mask_void,
                         void* workspace, hipStream_t stream) {
+  const uint32_t slice = slice_records(kSliceRecords);
   SplatWs ws = carve_ws(workspace, n, m);
-  const size_t base = splat_hdr_bytes() + (sizeof(int32_t) + sizeof(float)) * (size_t)n * (size_t)m;
-  BinWs bw = carve_bin_ws((char*)workspace + align16(base), n, m, height, width, channels);
+  Carver region = route_carver(workspace, n, m);
+  BinWs bw = bin_ws(region, n, m, height, width, channels, slice);
   const int tiles_x = ceil_div(width, kTileX), tiles_y = ceil_div(height, kTileY);
   const int ntiles = tiles_x * tiles_y, nb = n * ntiles;
   const bool ordered = !(output_void >= 0.0f);
-  const ChunkGeom cg = chunk_geom(m, n);
+  const ChunkGeom cg = chunk_geom(m, n, kChunkThreads);
   const uint64_t wmagic = ((uint64_t)1 << 40) / (uint64_t)width + 1;
   const dim3 g_pt((unsigned)cg.chunks, (unsigned)n);
   const int nparts = cg.chunks * n;
@@ -1258,7 +1172,6 @@ int launch_splat_binned(const float* coords, const float* offset, const T* feats
                        feats, m, ld, cg.per, channels, width, wmagic, ntiles, tiles_x, ws, bw);
   }
   const size_t tile_lds = 4 * (size_t)kTilePx * (1 + channels);
-  const uint32_t slice = slice_records();
   const int items = (int)resolve_items_max(nb, (int64_t)n * m, slice);
 #define SE3DS_RESOLVE(ORD, SC)                                                                   \
   hipLaunchKernelGGL((splat_tile_resolve_kernel<ORD, SC>), dim3(items), dim3(kResolveThreads),   \
@@ -1295,90 +1208,11 @@ int launch_splat_binned(const float* coords, const float* offset, const T* feats
 //                     registers between the z-min and the feature pass; the last workgroup to
 //                     finish folds the sink into flat pixel 0 (no separate launch).
 // Results are bit-identical to the other paths (min / max do not depend on the record order).
-constexpr int kPTileY = 16, kPTileX = 32, kPTilePx = kPTileY * kPTileX;   // 512 px
-constexpr int kPThreads = 512, kPPts = 4;
-constexpr int kPGroup = kPThreads * kPPts;     // points per workgroup iteration
+// (tiles, PackWs and its constants: splat_layout.h)
 constexpr int kPResolveThreads = 256;
 constexpr int kPStash = 4;                     // records per thread kept in registers
-constexpr uint32_t kPSlice = 4096;             // records per band workgroup aimed at
-constexpr int kPMaxChannels = 3;
-constexpr int kSinkSlots = 64;
 constexpr uint16_t kNoTile = 0xffffu;
 constexpr uint16_t kPendingTile = 0xfffeu;   // undecided by the fp32 screen: the exact pass fills it in
-
-struct PackWs {
-  uint32_t* ctl;          // [8]: 0 colscan tickets, 1 promise violations, 2 items, 3 resolve tickets
-  uint32_t* tile_count;   // [nb]
-  uint32_t* tile_start;   // [nb + 1] exclusive prefix of tile_count (published by the permute pass)
-  uint32_t* tile_lstart;  // [nb]  ... within the tile's group of 64
-  uint32_t* tile_litem;   // [nb]  first resolve item of the tile within its group
-  uint32_t* group_tot;    // [ngroups][2] records, items per group of 64 tiles
-  uint32_t* items;        // [items_max]  tile | band << 20 | log2(bands) << 24
-  uint32_t* hist;         // [n][chunks][ntiles]
-  uint32_t* fpart2;       // [kSinkSlots][C] ordered max feature of the occluded points (slot = item % kSinkSlots)
-  uint16_t* tile_pt;      // [n][mp]  tile of the point, kNoTile: no record
-  uint64_t* rec_pt;       // [n][mp]  records in point order
-  uint64_t* rec;          // [n * m]  records in tile order
-  int64_t mp;             // padded points per image (chunks * per)
-  uint32_t epoch;         // this call's promise epoch (kPromiseEpochWord)
-};
-__host__ __device__ inline ChunkGeom pack_geom(int64_t m, int n) {
-  int64_t cap = kMaxSinkBlocks / (n > 0 ? n : 1);
-  cap = cap < 1 ? 1 : (cap > kMaxChunks ? kMaxChunks : cap);
-  int64_t chunks = (m + kChunkPoints - 1) / kChunkPoints;
-  chunks = chunks < 1 ? 1 : (chunks > cap ? cap : chunks);
-  int64_t per = (m + chunks - 1) / chunks;
-  per = (per + kPGroup - 1) / kPGroup * kPGroup;
-  if (per < kPGroup) per = kPGroup;
-  chunks = (m + per - 1) / per;
-  ChunkGeom g;
-  g.chunks = (int)(chunks < 1 ? 1 : chunks);
-  g.per = per;
-  return g;
-}
-inline uint32_t pack_slice() {
-  static const uint32_t v = [] {
-    const char* e = getenv("SE3DS_SPLAT_SLICE");
-    const long x = e ? atol(e) : 0;
-    return (uint32_t)(x >= 16 ? x : (long)kPSlice);
-  }();
-  return v;
-}
-inline size_t pack_ws_bytes(int n, int64_t m, int height, int width) {
-  const size_t ntiles = (size_t)ceil_div(height, kPTileY) * ceil_div(width, kPTileX);
-  const size_t nb = (size_t)n * ntiles;
-  const ChunkGeom g = pack_geom(m, n);
-  const size_t mp = (size_t)g.chunks * (size_t)g.per;
-  const size_t items = (size_t)resolve_items_max((int64_t)nb, (int64_t)n * (m > 0 ? m : 0), pack_slice());
-  return 64 + align16(4 * nb) + align16(4 * (nb + 1)) + 2 * align16(4 * nb) +
-         align16(8 * (size_t)ceil_div(nb, 64)) + align16(4 * items) +
-         align16(4 * nb * (size_t)g.chunks) + align16(4 * kSinkSlots * kPMaxChannels) +
-         align16(2 * (size_t)n * mp) + align16(8 * (size_t)n * mp) +
-         align16(8 * (size_t)n * (size_t)(m > 0 ? m : 0));
-}
-inline PackWs carve_pack_ws(void* base, int n, int64_t m, int height, int width) {
-  const size_t ntiles = (size_t)ceil_div(height, kPTileY) * ceil_div(width, kPTileX);
-  const size_t nb = (size_t)n * ntiles;
-  const ChunkGeom g = pack_geom(m, n);
-  const size_t mp = (size_t)g.chunks * (size_t)g.per;
-  const size_t items = (size_t)resolve_items_max((int64_t)nb, (int64_t)n * (m > 0 ? m : 0), pack_slice());
-  char* p = (char*)base;
-  PackWs w;
-  w.ctl = (uint32_t*)p; p += 64;
-  w.tile_count = (uint32_t*)p; p += align16(4 * nb);
-  w.tile_start = (uint32_t*)p; p += align16(4 * (nb + 1));
-  w.tile_lstart = (uint32_t*)p; p += align16(4 * nb);
-  w.tile_litem = (uint32_t*)p; p += align16(4 * nb);
-  w.group_tot = (uint32_t*)p; p += align16(8 * (size_t)ceil_div(nb, 64));
-  w.items = (uint32_t*)p; p += align16(4 * items);
-  w.hist = (uint32_t*)p; p += align16(4 * nb * (size_t)g.chunks);
-  w.fpart2 = (uint32_t*)p; p += align16(4 * kSinkSlots * kPMaxChannels);
-  w.tile_pt = (uint16_t*)p; p += align16(2 * (size_t)n * mp);
-  w.rec_pt = (uint64_t*)p; p += align16(8 * (size_t)n * mp);
-  w.rec = (uint64_t*)p;
-  w.mp = (int64_t)mp;
-  return w;
-}
 
 // record = [ z bits (31) | pixel bit 8 ] [ pixel bits 0-7 | f0 | f1 | f2 ]
 __device__ __forceinline__ uint64_t pack_rec(uint32_t pix, float z, uint32_t f0, uint32_t f1, uint32_t f2) {
@@ -2035,23 +1869,21 @@ int launch_splat_packed(const float* coords, const float* offset, const T* feats
                         int64_t ld, int channels, int height, int width, float depth_scale,
                         float input_void, float output_void, float* depth, float* feat,
                         float* mask, float mask_void, void* workspace, hipStream_t stream) {
+  const uint32_t slice = slice_records(kPSlice);
   SplatWs ws = carve_ws(workspace, n, m);
-  const size_t base = splat_hdr_bytes() + (sizeof(int32_t) + sizeof(float)) * (size_t)n * (size_t)m;
-  PackWs pw = carve_pack_ws((char*)workspace + align16(base), n, m, height, width);
+  Carver region = route_carver(workspace, n, m);
+  PackWs pw = pack_ws(region, n, m, height, width, slice);
   pw.epoch = next_splat_epoch();
   const int tiles_x = ceil_div(width, kPTileX), tiles_y = ceil_div(height, kPTileY);
   const int ntiles = tiles_x * tiles_y, nb = n * ntiles;
-  const ChunkGeom cg = pack_geom(m, n);
+  const ChunkGeom cg = chunk_geom(m, n, kPGroup);
   const uint64_t wmagic = ((uint64_t)1 << 40) / (uint64_t)width + 1;
   const dim3 g_pt((unsigned)cg.chunks, (unsigned)n);
   const int nparts = cg.chunks * n;
-  const uint32_t slice = pack_slice();
   const int items = (int)resolve_items_max(nb, (int64_t)n * m, slice);
   const int vec = (ld % 4 == 0) && ((uintptr_t)coords % 16 == 0) &&
                   ((uintptr_t)feats % (sizeof(T) == 1 ? 4 : 16) == 0);
-  // (read per call: the parity tests switch the tap on for single calls)
-  const char* e_dbg = getenv("SE3DS_SPLAT_DEBUG");
-  const bool dbg = e_dbg && atoi(e_dbg) != 0;
+  const bool dbg = splat_debug_tap();
 #define SE3DS_P1(CC, DBG)                                                                         \
   hipLaunchKernelGGL((splat_pack_count_kernel<T, EQUIRECT, CC, DBG>), g_pt, dim3(kPThreads),      \
                      4 * ntiles, stream, coords, offset, feats, m, ld, cg.per, height, width,     \
@@ -2107,28 +1939,13 @@ int launch_splat_packed(const float* coords, const float* offset, const T* feats
 // Traffic per cfg5 render: 100 MB in + 38 MB of records out, 38 MB in + 42 MB out = 218 MB for 159 MB
 // algorithmic (the packed path: ~310 nominal, 382 measured).  min / max do not depend on the record
 // order: bit-identical to every other path.
-constexpr int kSMaxPx = 4096;            // pixels per supertile, upper bound (LDS tile of the resolve: 2 words per pixel)
-constexpr int kSDefaultPx = 2048;        // ... default: one full row of a 1024 x 2048 target
-constexpr int kSThreads = 512;           // S1 workgroup
+// (SortWs, SortGeom and the sizes that bound them: splat_layout.h)
 constexpr int kSQueue = 1024;            // S1: points waiting for the binary64 path (2 per thread)
-constexpr int kSMaxSuper = 2048;         // supertiles per image (S1 LDS histogram, 11-bit field)
-constexpr int kSMaxChunks = 4096;        // chunks per image (S2 LDS run prefix)
 constexpr int kRThreads = 512;           // S2 workgroup
 constexpr int kRStash = 12;              // S2: records per thread and batch (6 144 per workgroup: an average
                                          // supertile of cfg5 holds 4 096, its records stay in registers)
 constexpr uint32_t kSMetaNone = 0xffffffffu, kSMetaPending = 0xfffffffeu;
 
-struct SortWs {
-  uint32_t* ctl;      // [16]: 0 ticket, 1 promise violations (same slot as PackWs), 4.. pixel 0 (z, C feature words)
-  uint32_t* fpart2;   // [kSinkSlots][C] ordered max feature of the occluded points
-  uint32_t* runs;     // [n * nsuper][chunks]  offset << 16 | count
-  uint64_t* rec;      // [n * chunks][chunk_pts]
-  uint8_t* hi;        // [n * chunks][chunk_pts]
-  int chunks;         // per image
-  int chunk_pts;
-  int cstride;        // row length of `runs`: 8 * ceil(chunks / 8), see run_slot()
-  uint32_t epoch;     // this call's promise epoch (kPromiseEpochWord)
-};
 // Column of chunk c in a supertile's row of the run table.  A chunk is one S1 workgroup and
 // workgroup b runs on XCD b % 8 (observed placement, MI355X_MICROARCH.md; used for speed only): with
 // the chunks of one XCD next to each other, the 4-byte descriptors that XCD's workgroups write into
@@ -2140,100 +1957,9 @@ __host__ __device__ inline int run_chunk(int slot, int cstride) {
   const int per = cstride >> 3;
   return (slot % per) * 8 + slot / per;
 }
-// Supertile = `rows` FULL-WIDTH image rows (rows x width <= 2048 pixels; images wider than 2048 are
-// cut into column strips).  The shape matters: the pole rows of every SOURCE view (thousands of
-// pixels looking the same way) land on a near-vertical line of the target, and 32 x 128 supertiles
-// put 30 000 (random depth) to 86 000 (smooth room) records into the supertiles on that line against
-// a mean of 8 000 -- one workgroup then runs 4-10x longer than the rest.  A line crosses a row
-// once: full-row supertiles hold at most 1.35x (random) / 2.3x (room) the mean.
-struct SortGeom {
-  int pts, chunk_pts, chunks, super_w, rlog, super_x, super_y, nsuper, px;
-};
 inline int sort_env(const char* name, int dflt) {
   const char* e = getenv(name);
   return e ? atoi(e) : dflt;
-}
-// Geometry of one call.  Both kernels want TWO workgroups per CU (S1 is VALU- and S2 latency-bound: at one
-// 8-wave workgroup per CU every barrier and every load round trip is exposed).  Round 5 sized both for
-// the 4.2 M points of cfg5; at north_star's 512 x 1024 with two views that left 256 chunks and 256
-// supertiles for 256 CUs and each kernel took 16.8 us for a quarter of the work that takes 34-39 us at
-// 1024 x 2048 (profiles/r06_warp_512_*).  Now: points per thread = the largest of 16 / 8 / 4 that still
-// gives kSTargetWgs chunks, pixels per supertile = the largest of 2048 / 1024 / 512 that gives as
-// many supertiles (full image rows first, see above).
-constexpr int kSTargetWgs = 512;
-inline int sort_super_count(int height, int width, int super_px, int* super_w_out, int* rlog_out) {
-  int super_w = width <= super_px ? width : super_px;
-  if (width > super_w) {   // column strips of equal width (the last one may be ragged)
-    const int strips = ceil_div(width, super_w);
-    super_w = ceil_div(width, strips);
-  }
-  int rlog = 0;
-  while ((2 << rlog) * super_w <= super_px && (1 << rlog) < height) ++rlog;
-  if (super_w_out) *super_w_out = super_w;
-  if (rlog_out) *rlog_out = rlog;
-  return ceil_div(width, super_w) * ceil_div(height, 1 << rlog);
-}
-inline SortGeom sort_geom(int n, int64_t m, int height, int width, int pts_forced = 0, int px_forced = 0) {
-  // SE3DS_SPLAT_PTS forces 4 / 8 / 16 points per thread, SE3DS_SPLAT_SUPERPX 256 .. 4096 pixels per
-  // supertile (A/B runs and the parity tests' small images)
-  static const int pts_forced_env = sort_env("SE3DS_SPLAT_PTS", 0);
-  static const int px_forced_env = [] {
-    const int v = sort_env("SE3DS_SPLAT_SUPERPX", 0);
-    return v >= 256 && v <= kSMaxPx ? v : 0;
-  }();
-  const int64_t mm = m > 0 ? m : 1;
-  const int nn = n > 0 ? n : 1;
-  SortGeom g;
-  g.pts = pts_forced ? pts_forced
-                     : (pts_forced_env == 4 || pts_forced_env == 8 || pts_forced_env == 16) ? pts_forced_env : 0;
-  if (!g.pts) {
-    g.pts = 4;
-    for (int pts = 16; pts > 4; pts >>= 1)
-      if (ceil_div(mm, (int64_t)kSThreads * pts) * nn >= kSTargetWgs) {
-        g.pts = pts;
-        break;
-      }
-  }
-  g.chunk_pts = kSThreads * g.pts;
-  g.chunks = (int)ceil_div(mm, (int64_t)g.chunk_pts);
-  int super_px = px_forced ? px_forced : px_forced_env;
-  if (!super_px) {
-    super_px = kSDefaultPx;
-    while (super_px > 512 && (int64_t)nn * sort_super_count(height, width, super_px, nullptr, nullptr) < kSTargetWgs)
-      super_px >>= 1;
-  }
-  g.nsuper = sort_super_count(height, width, super_px, &g.super_w, &g.rlog);
-  g.super_x = ceil_div(width, g.super_w);
-  g.super_y = ceil_div(height, 1 << g.rlog);
-  g.px = g.super_w << g.rlog;
-  return g;
-}
-inline size_t sort_ws_bytes(int n, int64_t m, int height, int width) {
-  // (independent of the A/B environment switches: the worst case over every geometry a call may take)
-  size_t worst = 0;
-  for (int pts = 4; pts <= 16; pts <<= 1) {
-    const SortGeom g = sort_geom(n, m, height, width, pts, 256);   // (256-pixel supertiles: the longest run table)
-    const size_t b = 64 + align16(4 * kSinkSlots * kPMaxChannels) +
-                     align16(4 * (size_t)n * kSMaxSuper * (size_t)(8 * ceil_div(g.chunks, 8))) +
-                     align16(8 * (size_t)n * g.chunks * g.chunk_pts) +
-                     align16((size_t)n * g.chunks * g.chunk_pts);
-    worst = b > worst ? b : worst;
-  }
-  return worst;
-}
-inline SortWs carve_sort_ws(void* base, int n, const SortGeom& g) {
-  char* p = (char*)base;
-  SortWs w;
-  w.ctl = (uint32_t*)p; p += 64;
-  w.fpart2 = (uint32_t*)p; p += align16(4 * kSinkSlots * kPMaxChannels);
-  w.cstride = 8 * ceil_div(g.chunks, 8);
-  w.runs = (uint32_t*)p; p += align16(4 * (size_t)n * g.nsuper * w.cstride);
-  w.rec = (uint64_t*)p; p += align16(8 * (size_t)n * g.chunks * g.chunk_pts);
-  w.hi = (uint8_t*)p;
-  w.chunks = g.chunks;
-  w.chunk_pts = g.chunk_pts;
-  w.epoch = 0u;
-  return w;
 }
 
 #ifdef SE3DS_PROBE
@@ -3006,8 +2732,7 @@ int launch_splat_sorted_c(const float* coords, const float* offset, const T* fea
   const dim3 g_pt((unsigned)g.chunks, (unsigned)n);
   const int vec = (ld % 4 == 0) && ((uintptr_t)coords % 16 == 0) &&
                   ((uintptr_t)feats % (sizeof(T) == 1 ? 4 : 16) == 0);
-  const char* e_dbg = getenv("SE3DS_SPLAT_DEBUG");
-  const bool dbg = e_dbg && atoi(e_dbg) != 0;
+  const bool dbg = splat_debug_tap();
   const size_t lds1 = (size_t)g.chunk_pts * 9 + 4 * (size_t)g.nsuper;
   const size_t lds2 = 4 * (2 * (size_t)g.px + 2 * (size_t)g.chunks + 1);
   const void* k1 = dbg ? (const void*)splat_sort_kernel<T, EQUIRECT, C, true, PTS>
@@ -3034,8 +2759,8 @@ int launch_splat_sorted(const float* coords, const float* offset, const T* feats
                         float input_void, float output_void, float* depth, float* feat, float* mask,
                         float mask_void, void* workspace, const SortGeom& g, hipStream_t stream) {
   SplatWs ws = carve_ws(workspace, n, m);
-  const size_t base = splat_hdr_bytes() + (sizeof(int32_t) + sizeof(float)) * (size_t)n * (size_t)m;
-  SortWs sw = carve_sort_ws((char*)workspace + align16(base), n, g);
+  Carver region = route_carver(workspace, n, m);
+  SortWs sw = sort_ws(region, n, g, g.nsuper);
   sw.epoch = next_splat_epoch();
 #define SE3DS_S(CC, PP)                                                                           \
   return launch_splat_sorted_c<T, EQUIRECT, CC, PP>(coords, offset, feats, n, m, ld, height, width, \
@@ -3051,53 +2776,56 @@ int launch_splat_sorted(const float* coords, const float* offset, const T* feats
 #undef SE3DS_S
 }
 
+// The route switches, read once per process (the parity tests set them for child processes):
+// SE3DS_SPLAT_SCATTER keeps the global-atomic scatter version, SE3DS_SPLAT_PACKED=0 the 20-byte-record
+// path (A/B runs, parity tests), SE3DS_SPLAT_SORT the sorted chunks (0 off, 1 = when the image has enough
+// supertiles to fill the chip (default), 2 = always); SE3DS_SPLAT_PTS forces 4 / 8 / 16 points per
+// thread, SE3DS_SPLAT_SUPERPX 256 .. 4096 pixels per supertile (A/B runs and the parity tests' small images).
+inline const SplatSwitches& splat_switches() {
+  static const SplatSwitches switches = [] {
+    SplatSwitches s;
+    s.scatter = getenv("SE3DS_SPLAT_SCATTER") != nullptr;
+    const char* e = getenv("SE3DS_SPLAT_PACKED");
+    s.packed = !(e && atoi(e) == 0);
+    s.sort_mode = sort_env("SE3DS_SPLAT_SORT", 1);
+    s.pts = sort_env("SE3DS_SPLAT_PTS", 0);
+    if (s.pts != 4 && s.pts != 8 && s.pts != 16) s.pts = 0;
+    s.superpx = sort_env("SE3DS_SPLAT_SUPERPX", 0);
+    if (s.superpx < 256 || s.superpx > kSMaxPx) s.superpx = 0;
+    return s;
+  }();
+  return switches;
+}
+
 template <typename T, bool EQUIRECT>
 int launch_splat(const float* coords, const float* offset, const T* feats, int n, int64_t m,
                  int64_t ld,
                  int channels, int height, int width, float depth_scale, float input_void,
                  float output_void, float* depth, float* feat, float* mask, float mask_void,
                  void* workspace, hipStream_t stream, bool byte_range = false) {
-  {
-    static const bool no_bin = getenv("SE3DS_SPLAT_SCATTER") != nullptr;
-    // 8-byte packed records (round 3): features of valid points are bytes by type (uint8) or by
-    // the caller's promise (int32 | SE3DS_FEAT_BYTE_RANGE), <= 3 channels, non-negative output
-    // void.  SE3DS_SPLAT_PACKED=0 keeps the 20-byte-record path (A/B runs, parity tests).
-    if constexpr (!std::is_same<T, float>::value) {
-      static const bool no_pack = [] {
-        const char* e = getenv("SE3DS_SPLAT_PACKED");
-        return e && atoi(e) == 0;
-      }();
-      const int64_t ptiles = (int64_t)ceil_div(height, kPTileY) * ceil_div(width, kPTileX);
-      // round 4: sorted chunks + gathering resolve (SE3DS_SPLAT_SORT: 0 off, 1 = when the image has
-      // enough supertiles to fill the chip (default), 2 = always)
-      static const int sort_mode = sort_env("SE3DS_SPLAT_SORT", 1);
-      const bool packable = !no_bin && !no_pack && m > 0 && channels <= kPMaxChannels &&
-          (std::is_same<T, uint8_t>::value || byte_range) && output_void >= 0.0f &&
-          (int64_t)n * m < ((int64_t)1 << 31) && (int64_t)height * width * width < ((int64_t)1 << 40);
-      if (packable && sort_mode != 0) {
-        const SortGeom sg = sort_geom(n, m, height, width);
-        if (sg.nsuper <= kSMaxSuper && sg.chunks <= kSMaxChunks &&
-            (int64_t)sg.chunks * n <= kMaxSinkBlocks && (int64_t)n * sg.nsuper < ((int64_t)1 << 24) &&
-            (sort_mode == 2 || (int64_t)n * sg.nsuper >= 128))
-          return launch_splat_sorted<T, EQUIRECT>(coords, offset, feats, n, m, ld, channels, height,
-                                                  width, depth_scale, input_void, output_void, depth,
-                                                  feat, mask, mask_void, workspace, sg, stream);
-      }
-      if (!no_bin && !no_pack && m > 0 && channels <= kPMaxChannels && ptiles <= kMaxTiles &&
-          (std::is_same<T, uint8_t>::value || byte_range) && output_void >= 0.0f &&
-          (int64_t)n * ptiles < ((int64_t)1 << 20) && (int64_t)n * m < ((int64_t)1 << 31) &&
-          (int64_t)height * width * width < ((int64_t)1 << 40))
+  constexpr bool kFloat = std::is_same<T, float>::value;
+  const SplatChoice choice = splat_route(
+      kFloat ? SplatFeat::Float : std::is_same<T, uint8_t>::value ? SplatFeat::Uint8 : SplatFeat::Int32,
+      byte_range, n, m, channels, height, width, output_void, splat_switches());
+  switch (choice.route) {
+    case SplatRoute::Sorted:   // (8-byte records: never float features)
+      if constexpr (!kFloat)
+        return launch_splat_sorted<T, EQUIRECT>(coords, offset, feats, n, m, ld, channels, height,
+                                                width, depth_scale, input_void, output_void, depth,
+                                                feat, mask, mask_void, workspace, choice.sort, stream);
+      break;
+    case SplatRoute::Packed:
+      if constexpr (!kFloat)
         return launch_splat_packed<T, EQUIRECT>(coords, offset, feats, n, m, ld, channels, height,
                                                 width, depth_scale, input_void, output_void, depth,
                                                 feat, mask, mask_void, workspace, stream);
-    }
-    const int64_t ntiles = (int64_t)ceil_div(height, kTileY) * ceil_div(width, kTileX);
-    if (!no_bin && m > 0 && channels <= kMaxBinChannels && ntiles <= kMaxTiles &&
-        (int64_t)n * m < ((int64_t)1 << 31) &&
-        (int64_t)height * width * width < ((int64_t)1 << 40))
+      break;
+    case SplatRoute::Binned:
       return launch_splat_binned<T, EQUIRECT>(coords, offset, feats, n, m, ld, channels, height, width,
                                               depth_scale, input_void, output_void, depth, feat,
                                               mask, mask_void, workspace, stream);
+    case SplatRoute::Scatter:
+      break;
   }
   SplatWs ws = carve_ws(workspace, n, m);
   const int64_t npx = (int64_t)n * height * width;
@@ -3712,16 +3440,8 @@ int se3ds_unproject_equirect(const void* feats, int feat_dtype, const float* dep
 }
 
 size_t se3ds_splat_workspace_bytes(int n, int64_t m, int height, int width, int channels) {
-  const size_t base = splat_hdr_bytes() +
-                      (sizeof(int32_t) + sizeof(float)) * (size_t)n * (size_t)(m > 0 ? m : 0);
-  const int c = channels > 0 ? channels : 1;
-  const size_t three_pass = bin_ws_bytes(n, m, height, width, c);
-  const size_t packed = pack_ws_bytes(n, m, height, width);
-  const size_t sorted = sort_ws_bytes(n, m, height, width);
-  size_t bins = three_pass;
-  if (packed > bins) bins = packed;
-  if (sorted > bins) bins = sorted;
-  return align16(base) + bins + 16;
+  return splat_workspace_bytes(n, m, height, width, channels, slice_records(kSliceRecords),
+                               slice_records(kPSlice));
 }
 
 int se3ds_project_equirect(const float* xyz1, const float* offset, const void* feats,
@@ -3804,9 +3524,8 @@ int se3ds_feats_byte_range(const void* feats, int feat_dtype, int64_t count, flo
 int se3ds_splat_promise_broken(const void* workspace, int n, int64_t m, uint32_t* broken_out,
                                void* stream) {
   if (n <= 0 || m <= 0 || !broken_out) return SE3DS_E_BADSHAPE;
-  const size_t base = splat_hdr_bytes() + (sizeof(int32_t) + sizeof(float)) * (size_t)n * (size_t)m;
-  PackWs pw;
-  pw.ctl = (uint32_t*)((char*)const_cast<void*>(workspace) + align16(base));
+  PackWs pw;   // (ctl is the first array of the packed and of the sorted region)
+  pw.ctl = route_carver(const_cast<void*>(workspace), n, m).take<uint32_t>(kCtlWords);
   hipLaunchKernelGGL(splat_promise_kernel, dim3(1), dim3(1), 0, as_stream(stream), pw, broken_out);
   return check_launch("splat_promise_broken");
 }

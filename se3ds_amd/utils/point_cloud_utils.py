@@ -62,8 +62,9 @@ def _dev_key(device) -> str:
 def _workspace(nbytes: int, device) -> torch.Tensor:
   """Grow-only scratch buffer per device (keeps allocation out of the trajectory loop).  Its
   256-byte header is zeroed at creation: header word 3 is the library's STICKY promise-violation
-  flag (include/se3ds_hip.h, se3ds_splat_promise_sticky); words 1 and 2 are the single-launch
-  splat's grid barrier and ticket (zero at rest)."""
+  flag (include/se3ds_hip.h, se3ds_splat_promise_sticky).  Word 0 and bytes 16..255 hold the sink
+  pixel's depth and features, which the calls that use them initialise themselves; words 1 and 2
+  are unused (csrc/splat_layout.h, SplatWs)."""
   key = _dev_key(device)
   ws = _workspaces.get(key)
   if ws is None or ws.numel() < nbytes:
