@@ -7,6 +7,8 @@ each op appends a closure; gradient accumulation for tensors with several consum
 """
 import math
 import threading
+from collections import namedtuple
+from types import SimpleNamespace
 from typing import List, Optional
 
 import numpy as np
@@ -26,13 +28,8 @@ def _L():
   return _lib.lib()
 
 
-def _log_collective(kind, numel):
-  from se3ds_amd.trainers import dist_utils   # (late: dist_utils does not import this module)
-  dist_utils.log_collective(kind, numel)
-
-
 def _all_reduce_sum(t, group, kind):
-  from se3ds_amd.trainers import dist_utils
+  from se3ds_amd.trainers import dist_utils   # (late: dist_utils does not import this module)
   dist_utils.all_reduce_sum(t, group, kind)
 
 
@@ -195,6 +192,12 @@ def truncated_normal_init(shape, gen, std=0.05):
 
 
 # --------------------------------------------------------------------------------- context
+# Hand-overs between conv2d and norm_act on a Var; RowSink.bias_grad() is lazy.
+BnSrc = namedtuple('BnSrc', 'x amask mean rstd act alpha')
+BnStats = namedtuple('BnStats', 'rows gver')
+RowSink = namedtuple('RowSink', 'out_scale bias_scale bias_grad')
+
+
 class Var:
   """Activation handle: NHWC tensor in the compute dtype plus its (lazy) gradient."""
   __slots__ = ('data', '_grad', 'gver', 'requires_grad', 'col_stats', 'grad_pre_act', 'shared',
@@ -204,13 +207,10 @@ class Var:
     self.data = data
     self._grad = None
     self.gver = 0           # bumped by every write to .grad (assignment or in-place accumulation)
-    self.bn_src = None      # batch-norm outputs: (x, act mask, mean, rstd, act, alpha) of the norm
-    self.bn_stats = None    # ... (stats rows, gver): backward statistics a data-gradient epilogue
-                            # took from the gradient it stored (valid while gver is unchanged)
-    self.row_sink = None    # outputs of biased partial convs: (out row scale, bias row scale,
-                            # store, bias name) -- a batch norm that is the only consumer stores
-                            # its dx pre-scaled and writes the bias gradient (norm_bwd_apply_rows)
-    self.grad_scaled = None   # ... gver at which it did
+    self.bn_src = None      # batch-norm outputs: BnSrc, the norm's operands for a consuming conv
+    self.bn_stats = None    # ... BnStats that conv's data gradient took from the gradient it stored
+    self.row_sink = None    # outputs of biased partial convs: RowSink for a batch norm behind it
+    self.grad_scaled = None   # ... gver at which that norm stored the gradient pre-scaled
     self.requires_grad = requires_grad
     self.col_stats = None   # conv outputs: partial column sums for a following batch norm
     self.grad_pre_act = False   # the consumer already applied this tensor's activation derivative
@@ -230,6 +230,21 @@ class Var:
     self._grad = g
     self.gver += 1
 
+  def take_bn_stats(self):
+    """bn_stats' rows if the gradient is still the one they were taken from, else None; clears it."""
+    s, self.bn_stats = self.bn_stats, None
+    return s.rows if s is not None and s.gver == self.gver else None
+
+  def take_grad_scaled(self, who):
+    """True if a norm stored the gradient pre-scaled and nothing wrote to it since; clears it."""
+    gs = self.grad_scaled
+    if gs is not None and gs != self.gver:
+      # ... and something else wrote to it afterwards: the sum can no longer be un-mixed
+      raise RuntimeError(f'{who}: pre-scaled output gradient was modified by a second '
+                         'consumer (set SE3DS_FUSED_ROW_SCALE=0)')
+    self.grad_scaled = None
+    return gs is not None
+
 
 class Ctx:
   """Per-call execution context: compute dtype, training flag, tape, replica group."""
@@ -248,6 +263,10 @@ class Ctx:
     self.on_segment = None    # callback(name): a top-level module's parameter gradients are final
     self.batch_limit = None   # backward passes that only concern the first samples of the batch
     self.act_taps = None      # tests: dict layer name -> activated output (sign decisions)
+    self.taps = None          # tests: dict the generator fills with its encoder outputs
+    self.bn_use_moving = False   # tests / tools: batch norms use moving statistics while training
+    self.after_collective = None   # callback() behind every all-reduce issued through this context
+    self._mask_cache = {}     # partial-conv mask windows shared by layers (_partial_masks)
     # Independent branches of the graph (the generator's two decoders) on their own HIP streams:
     # {tag: torch.cuda.Stream}, None = everything on the current stream.  Ops record the branch
     # they ran in; backward() replays each branch's closures on its stream (see branch()).
@@ -397,9 +416,8 @@ class Ctx:
 
   def _after_collective(self):
     self.collectives += 1
-    cb = getattr(self, 'after_collective', None)
-    if cb is not None:
-      cb()   # (GradSync.pump: pending gradient buckets go out behind this collective)
+    if self.after_collective is not None:
+      self.after_collective()   # (GradSync.pump: pending gradient buckets go out behind this one)
 
   def allreduce_sum(self, t):
     if self.world > 1:
@@ -757,6 +775,7 @@ class ConvLayer:
       store.add(name + '/u', (1, cout), truncated_normal_init, trainable=False)
     self._copies = {}   # dtype -> (version, wt, wn)
     self.sn = None      # spectral scratch: dict(v, uhat, sig, part, vpart)
+    self._wgrad_slab = None   # slab scratch of the deferred weight-gradient reduction (_wgrad)
 
   @property
   def kernel(self):
@@ -855,6 +874,8 @@ class SpectralGroup:
     self.table = torch.tensor(rows, dtype=torch.int64, device=device) if rows else None
     self._eff = [i for i, l in enumerate(self.layers) if l.kind == 'spectral']
     self._eff_table = None
+    self._tensor_sn = None   # tensor_sn()'s table, built on first use
+    self._seg_tables = {}    # backward_fixup(prefix): prefix -> that module's rows of eff_table
 
   @property
   def eff_table(self):
@@ -882,7 +903,7 @@ class SpectralGroup:
     tab = self.eff_table
     if tab is None:
       return None
-    if getattr(self, '_tensor_sn', None) is None:
+    if self._tensor_sn is None:
       nf = tab.shape[1]
       index = {n_: t for t, n_ in enumerate(store.trainable_names)}
       rows = [0] * len(store.trainable_names)
@@ -900,7 +921,7 @@ class SpectralGroup:
     if tab is None:
       return
     if prefix is not None:
-      cache = self.__dict__.setdefault('_seg_tables', {})
+      cache = self._seg_tables
       if prefix not in cache:
         pres = prefix if isinstance(prefix, (tuple, list)) else (prefix,)
         rows = [j for j, i in enumerate(self._eff)
@@ -962,7 +983,7 @@ def _wgrad(ctx, layer, args, wsz):
     _chk(L.se3ds_conv2d_wgrad(*args, None, 0, ws.data_ptr(), ws.numel(), _lib.stream()),
          'se3ds_conv2d_wgrad')
     return
-  ws = layer.__dict__.get('_wgrad_slab')
+  ws = layer._wgrad_slab
   if ws is None or ws.numel() < wsz:
     ws = torch.empty((int(wsz),), dtype=torch.uint8, device=ctx.device)
     layer._wgrad_slab = ws
@@ -1013,6 +1034,50 @@ def _reduce_rows(ctx, rows):
          'se3ds_wgrad_reduce_multi')
 
 
+# The argument prefix the convolution entry points of the C ABI share (se3ds_hip.h), spliced as *geo.
+_Geom = namedtuple('_Geom', 'code n h w cin ho wo cout kh kw stride pad_t pad_l wrap')
+
+def _partial_masks(ctx, mask, geo, recording):
+  """(ratio, update_mask, ru, bu, in_mask) of a partial conv; in_mask: what the kernels multiply x by."""
+  _, n, h, w, _, ho, wo, _, k, _, s, pt, pl, wrap = geo
+  m = in_mask = mask
+  if m is None:
+    m = torch.empty((n, h, w), dtype=torch.float32, device=ctx.device)
+    _chk(_L().se3ds_fill(m.data_ptr(), _lib.F32, m.numel(), 1.0, _lib.stream()), 'se3ds_fill')
+  # The window sums depend on the mask and the geometry only: layers that see the SAME mask tensor
+  # with the same geometry share one launch (round 5).  In a ResNet stack the 1x1 convs pass a
+  # binary mask through unchanged (update_mask = clip(mask, 0, 1) = mask), so with the alias below
+  # conv3 of a block, the next block's conv1 and its downsample conv hit the same entry: 115 ->
+  # ~50 launches of 5 us (+ a dependent-launch boundary each) on the encoder's serial path.
+  cache = ctx._mask_cache if mask is not None else None
+  key = (m.data_ptr(), tuple(m.shape), k, s, pt, pl, wrap, ho, wo, bool(recording))
+  ent = cache.get(key) if cache is not None and _MASK_CACHE else None
+  if ent is None:
+    ratio, um, ru, bu = mask_window(ctx, m, n, h, w, ho, wo, k, s, pt, pl, wrap, recording)
+    if (cache is not None and _MASK_CACHE and ctx.binary_masks and k == 1 and s == 1 and pt == 0 and
+        pl == 0):
+      um = m   # (exactly the kernel's output for a {0, 1} mask: the chain keeps ONE tensor)
+    if cache is not None:
+      cache[key] = (ratio, um, ru, bu, m)   # (m: keeps the keyed storage alive)
+  else:
+    ratio, um, ru, bu = ent[:4]
+  if in_mask is not None and k == 1 and ctx.binary_masks and _DROP_1X1_MASK:
+    # A 1 x 1 partial conv with a {0, 1} mask does not need x * mask: its window IS the pixel, so
+    # ratio = update_mask = 0 exactly where the mask is 0 and the epilogue's `* ratio` (and
+    # `* update_mask` behind the bias) zeroes those outputs whatever the product was -- PROVIDED the
+    # activation there is finite: 0 * Inf and 0 * NaN are NaN, so a non-finite value at a masked pixel,
+    # which the input mask used to zero, would now reach y, the fused statistics and (dy = 0, x read
+    # unmasked) the weight gradient.  Every input of a 1 x 1 partial conv in this network is a
+    # batch-norm + ReLU output or the finite network input, and a non-finite activation anywhere else
+    # already poisons the batch statistics of its layer; SE3DS_DROP_1X1_MASK=0 keeps the product.
+    # Backward, dy * ratio * update_mask is 0 there, so neither the weight gradient
+    # nor dx sees the masked pixels.  Without the mask the kernels skip one dependent global load
+    # (mask -> source address of the first LDS-DMA) at the head of every workgroup: ~10 us of a
+    # 60 us launch on the encoder's 512 <-> 2048 bottleneck convs.
+    in_mask = None
+  return ratio, um, ru, bu, in_mask
+
+
 def conv2d(ctx: Ctx, x: Var, layer: ConvLayer, pad=0, wrap=False, mask=None, act=ACT_NONE,
            alpha=0.0):
   """PadLayer(pad, circular=wrap) + conv (+ partial-conv renormalisation / spectral scale /
@@ -1024,51 +1089,13 @@ def conv2d(ctx: Ctx, x: Var, layer: ConvLayer, pad=0, wrap=False, mask=None, act
   k, s = layer.k, layer.stride
   ho, pt = conv_out_size(h, k, s, layer.padding, pad)
   wo, pl = conv_out_size(w, k, s, layer.padding, pad)
-  wrap = bool(wrap and pad > 0)
+  geo = _Geom(ctx.code, n, h, w, cin, ho, wo, layer.cout, k, k, s, pt, pl,
+              1 if (wrap and pad > 0) else 0)
   L = _L()
   wt, wn = layer.operands(ctx)
   partial = layer.kind in ('partial', 'partial_spectral')
   recording = ctx.tape is not None
-  ratio = um = ru = bu = None
-  in_mask = None
-  if partial:
-    m = mask
-    if m is None:
-      m = torch.empty((n, h, w), dtype=torch.float32, device=ctx.device)
-      _chk(L.se3ds_fill(m.data_ptr(), _lib.F32, m.numel(), 1.0, _lib.stream()), 'se3ds_fill')
-    else:
-      in_mask = m
-    # The window sums depend on the mask and the geometry only: layers that see the SAME mask tensor
-    # with the same geometry share one launch (round 5).  In a ResNet stack the 1x1 convs pass a
-    # binary mask through unchanged (update_mask = clip(mask, 0, 1) = mask), so with the alias below
-    # conv3 of a block, the next block's conv1 and its downsample conv hit the same entry: 115 ->
-    # ~50 launches of 5 us (+ a dependent-launch boundary each) on the encoder's serial path.
-    cache = ctx.__dict__.setdefault('_mask_cache', {}) if mask is not None else None
-    key = (m.data_ptr(), tuple(m.shape), k, s, pt, pl, wrap, ho, wo, bool(recording))
-    ent = cache.get(key) if cache is not None and _MASK_CACHE else None
-    if ent is None:
-      ratio, um, ru, bu = mask_window(ctx, m, n, h, w, ho, wo, k, s, pt, pl, wrap, recording)
-      if (cache is not None and _MASK_CACHE and ctx.binary_masks and k == 1 and s == 1 and pt == 0 and
-          pl == 0):
-        um = m   # (exactly the kernel's output for a {0, 1} mask: the chain keeps ONE tensor)
-      if cache is not None:
-        cache[key] = (ratio, um, ru, bu, m)   # (m: keeps the keyed storage alive)
-    else:
-      ratio, um, ru, bu = ent[:4]
-    if in_mask is not None and k == 1 and ctx.binary_masks and _DROP_1X1_MASK:
-      # A 1 x 1 partial conv with a {0, 1} mask does not need x * mask: its window IS the pixel, so
-      # ratio = update_mask = 0 exactly where the mask is 0 and the epilogue's `* ratio` (and
-      # `* update_mask` behind the bias) zeroes those outputs whatever the product was -- PROVIDED the
-      # activation there is finite: 0 * Inf and 0 * NaN are NaN, so a non-finite value at a masked pixel,
-      # which the input mask used to zero, would now reach y, the fused statistics and (dy = 0, x read
-      # unmasked) the weight gradient.  Every input of a 1 x 1 partial conv in this network is a
-      # batch-norm + ReLU output or the finite network input, and a non-finite activation anywhere else
-      # already poisons the batch statistics of its layer; SE3DS_DROP_1X1_MASK=0 keeps the product.
-      # Backward, dy * ratio * update_mask is 0 there, so neither the weight gradient
-      # nor dx sees the masked pixels.  Without the mask the kernels skip one dependent global load
-      # (mask -> source address of the first LDS-DMA) at the head of every workgroup: ~10 us of a
-      # 60 us launch on the encoder's 512 <-> 2048 bottleneck convs.
-      in_mask = None
+  ratio, um, ru, bu, in_mask = _partial_masks(ctx, mask, geo, recording) if partial else (None,) * 5
   # SpectralConv convolves with W/(sigma+eps); PartialSpectralConv with the raw kernel.
   scale = layer.sn['sig'][1:] if layer.kind == 'spectral' else None
   bias = layer.bias
@@ -1079,169 +1106,149 @@ def conv2d(ctx: Ctx, x: Var, layer: ConvLayer, pad=0, wrap=False, mask=None, act
   # a following SyncBatchNormalization needs) do so; norm_act picks them up from the Var.
   stats_rows = 0
   # (the sums are taken over the stored, activated outputs, so a fused activation is fine)
-  if ctx.training and recording and not getattr(ctx, 'bn_use_moving', False):
+  if ctx.training and recording and not ctx.bn_use_moving:
     stats_rows = int(L.se3ds_conv2d_fwd_stats_rows(ctx.code, n, cin, ho, wo, layer.cout, k, k, s,
                                                    1 if in_mask is not None else 0,
                                                    1 if ctx.binary_masks else 0))
-  stats = None
+  args = (xd.data_ptr(), wt.data_ptr(), y.data_ptr(), *geo, _lib.ptr(in_mask),
+          1 if ctx.binary_masks else 0, _lib.ptr(scale), _lib.ptr(bias), _lib.ptr(ratio),
+          _lib.ptr(um if (partial and bias is not None) else None), act, float(alpha))
+  out = Var(y)
   with _Timed('fwd', flops, tag):
     if stats_rows > 0:
-      stats = torch.empty((stats_rows, 2, layer.cout), dtype=torch.float32, device=ctx.device)
-      _chk(L.se3ds_conv2d_fwd_stats(xd.data_ptr(), wt.data_ptr(), y.data_ptr(), ctx.code, n, h, w,
-                                    cin, ho, wo, layer.cout, k, k, s, pt, pl, 1 if wrap else 0,
-                                    _lib.ptr(in_mask), 1 if ctx.binary_masks else 0,
-                                    _lib.ptr(scale), _lib.ptr(bias), _lib.ptr(ratio),
-                                    _lib.ptr(um if (partial and bias is not None) else None), act,
-                                    float(alpha), stats.data_ptr(), _lib.stream()),
+      # [rows][2][cout] partial (sum, sum of squares) of y
+      out.col_stats = torch.empty((stats_rows, 2, layer.cout), dtype=torch.float32, device=ctx.device)
+      _chk(L.se3ds_conv2d_fwd_stats(*args, out.col_stats.data_ptr(), _lib.stream()),
            'se3ds_conv2d_fwd_stats')
     else:
-      _chk(L.se3ds_conv2d_fwd(xd.data_ptr(), wt.data_ptr(), y.data_ptr(), ctx.code, n, h, w, cin,
-                              ho, wo, layer.cout, k, k, s, pt, pl, 1 if wrap else 0,
-                              _lib.ptr(in_mask), 1 if ctx.binary_masks else 0, _lib.ptr(scale),
-                              _lib.ptr(bias), _lib.ptr(ratio),
-                              _lib.ptr(um if (partial and bias is not None) else None), act,
-                              float(alpha), _lib.stream()), 'se3ds_conv2d_fwd')
-  out = Var(y)
+      _chk(L.se3ds_conv2d_fwd(*args, _lib.stream()), 'se3ds_conv2d_fwd')
   if act != ACT_NONE and ctx.act_taps is not None:
     ctx.act_taps[layer.name] = y
-  if stats is not None:
-    out.col_stats = stats   # [rows][2][cout] partial (sum, sum of squares) of y
   if (recording and partial and bias is not None and ctx.binary_masks and act == ACT_NONE and
       layer.cout % 8 == 0 and xd.dtype == torch.bfloat16):
-    out.row_sink = (ru, bu, layer.store, layer.name + '/bias')
+    out.row_sink = RowSink(ru, bu, lambda: layer.store.grad_views[layer.name + '/bias'])
   if recording:
-    def bwd(n=n):
-      dy = out.grad
-      pre_scaled = out.grad_scaled is not None and out.grad_scaled == out.gver
-      if out.grad_scaled is not None and not pre_scaled:
-        # a norm stored its dx already multiplied by this conv's row scale and something else
-        # wrote to the gradient afterwards: the sum can no longer be un-mixed -- fail loudly
-        raise RuntimeError(f'{layer.name}: pre-scaled output gradient was modified by a second '
-                           'consumer (set SE3DS_FUSED_ROW_SCALE=0)')
-      out.grad_scaled = None
-      out.grad = None
-      if dy is None:
-        return
-      # ctx.batch_limit: this backward pass only concerns the first `limit` samples (their
-      # gradients do not depend on the others: no batch statistics on this path)
-      lim = getattr(ctx, 'batch_limit', None)
-      if lim is not None and lim < n:
-        assert not partial and dy.shape[0] == lim and not ctx.param_grads
-        n = lim
-      if act != ACT_NONE and not out.grad_pre_act:
-        _chk(L.se3ds_act_bwd(dy.data_ptr(), y.data_ptr(), ctx.code, dy.numel(), act, float(alpha),
-                             dy.data_ptr(), _lib.stream()), 'se3ds_act_bwd')
-      out.grad_pre_act = False
-      rows = n * ho * wo
-      row_scale = None
-      dys = dy
-      st = layer.store
-      bias_done = False
-      if partial and pre_scaled:
-        # the batch norm behind this conv stored its dx already multiplied by ratio * update_mask
-        # and wrote the bias gradient (se3ds_norm_bwd_apply_rows): no pass over dy here
+    sv = SimpleNamespace(ctx=ctx, x=x, out=out, layer=layer, geo=geo, act=act, alpha=float(alpha),
+                         partial=partial, ratio=ratio, ru=ru, bu=bu, in_mask=in_mask, wn=wn,
+                         scale=scale, flops=flops, tag=tag)
+    ctx.record(lambda: _conv2d_bwd(sv))   # (the tape keeps sv's tensors alive)
+  return (out, um) if partial else out
+
+
+def _conv2d_bwd(sv):
+  ctx, out, layer, geo, L = sv.ctx, sv.out, sv.layer, sv.geo, _L()
+  dy = out.grad
+  pre_scaled = out.take_grad_scaled(layer.name)
+  out.grad = None
+  if dy is None:
+    return
+  # ctx.batch_limit: this backward pass only concerns the first `limit` samples (their
+  # gradients do not depend on the others: no batch statistics on this path)
+  lim = ctx.batch_limit
+  if lim is not None and lim < geo.n:
+    assert not sv.partial and dy.shape[0] == lim and not ctx.param_grads
+    geo = geo._replace(n=lim)
+  if sv.act != ACT_NONE and not out.grad_pre_act:
+    _chk(L.se3ds_act_bwd(dy.data_ptr(), out.data.data_ptr(), ctx.code, dy.numel(), sv.act,
+                         sv.alpha, dy.data_ptr(), _lib.stream()), 'se3ds_act_bwd')
+  out.grad_pre_act = False
+  rows, cout = geo.n * geo.ho * geo.wo, geo.cout
+  dys, row_scale, bias_done = dy, None, False
+  if sv.partial and pre_scaled:
+    # the batch norm behind this conv stored its dx already multiplied by ratio * update_mask
+    # and wrote the bias gradient (se3ds_norm_bwd_apply_rows): no pass over dy here
+    bias_done = True
+  elif sv.partial:
+    row_scale = sv.ru if layer.has_bias else sv.ratio
+    if ctx.binary_masks:
+      # pre-scale dy once so that wgrad / dgrad can take the LDS-DMA kernels
+      dys = ctx.empty(dy.shape)
+      if ctx.param_grads and layer.has_bias and dy.dtype == torch.bfloat16 and cout % 8 == 0:
+        # ... and take the bias gradient's column sums from the same read of dy
+        sums = torch.empty((1, 2, cout), dtype=torch.float32, device=ctx.device)
+        ws = ctx.ws('norm', L.se3ds_norm_workspace_bytes(1, cout))
+        _chk(L.se3ds_colsum_row_scale(dy.data_ptr(), ctx.code, rows, cout, sv.bu.data_ptr(),
+                                      row_scale.data_ptr(), dys.data_ptr(), sums.data_ptr(),
+                                      layer.store.grad_views[layer.name + '/bias'].data_ptr(),
+                                      ws.data_ptr(), ws.numel(), _lib.stream()),
+             'se3ds_colsum_row_scale')
         bias_done = True
-      elif partial:
-        row_scale = ru if bias is not None else ratio
-        if ctx.binary_masks:
-          # pre-scale dy once so that wgrad / dgrad can take the LDS-DMA kernels
-          dys = ctx.empty(dy.shape)
-          if (ctx.param_grads and bias is not None and dy.dtype == torch.bfloat16 and
-              layer.cout % 8 == 0):
-            # ... and take the bias gradient's column sums from the same read of dy
-            sums = torch.empty((1, 2, layer.cout), dtype=torch.float32, device=ctx.device)
-            ws = ctx.ws('norm', L.se3ds_norm_workspace_bytes(1, layer.cout))
-            _chk(L.se3ds_colsum_row_scale(dy.data_ptr(), ctx.code, rows, layer.cout, bu.data_ptr(),
-                                          row_scale.data_ptr(), dys.data_ptr(), sums.data_ptr(),
-                                          st.grad_views[layer.name + '/bias'].data_ptr(),
-                                          ws.data_ptr(), ws.numel(), _lib.stream()),
-                 'se3ds_colsum_row_scale')
-            bias_done = True
-          else:
-            _chk(L.se3ds_row_scale(dy.data_ptr(), ctx.code, rows, layer.cout, row_scale.data_ptr(),
-                                   dys.data_ptr(), _lib.stream()), 'se3ds_row_scale')
-          row_scale = None
-      if ctx.param_grads:
-        if bias is not None and not bias_done:
-          _colsum(ctx, dy.data_ptr(), ctx.code, rows, layer.cout,
-                  row_scale=bu if partial else None, out=st.grad_views[layer.name + '/bias'])
-        gk = st.grad_views[layer.name + '/kernel']
-        thin_out = (layer.cout <= 16 and cin > 16 and s == 1 and ho == h and wo == w and
-                    pt == pl and not wrap and not partial)
-        if thin_out:
-          # 128->3 / 128->1 output convs: role-swapped weight gradient (x streamed once)
-          wsz = L.se3ds_conv2d_wgrad_swapped_workspace_bytes(n, h, w, cin, layer.cout, k)
-          ws = _global_ws(ctx.device, 'wgrad', wsz)
-          with _Timed('wgrad', flops, tag):
-            _chk(L.se3ds_conv2d_wgrad_swapped(xd.data_ptr(), dys.data_ptr(), gk.data_ptr(),
-                                              ctx.code, n, h, w, cin, layer.cout, k, pt, 0,
-                                              ws.data_ptr(), ws.numel(), _lib.stream()),
-                 'se3ds_conv2d_wgrad_swapped')
-        else:
-          wsz = L.se3ds_conv2d_wgrad_workspace_bytes(n, ho, wo, cin, layer.cout, k, k)
-          with _Timed('wgrad', flops, tag):
-            _wgrad(ctx, layer, (xd.data_ptr(), dys.data_ptr(), gk.data_ptr(), ctx.code, n, h,
-                                w, cin, ho, wo, layer.cout, k, k, s, pt, pl,
-                                1 if wrap else 0, _lib.ptr(in_mask),
-                                1 if ctx.binary_masks else 0, _lib.ptr(row_scale)), wsz)
-      if x.requires_grad:
-        prev = x.grad
-        shape = (n,) + tuple(xd.shape[1:])
-        have_prev = prev is not None and tuple(prev.shape) == shape and prev.dtype == xd.dtype
-        bn_rows = 0
-        if (x.bn_src is not None and row_scale is None and lim is None and _FUSED_BN_BWD and
-            (prev is None or have_prev)):
-          bn_rows = int(L.se3ds_conv2d_dgrad_bnstats_rows(ctx.code, n, h, w, cin, layer.cout, k, k,
-                                                          s, 0))
-        if bn_rows > 0:
-          # x is a batch norm's output: this data gradient also takes the norm's backward
-          # statistics from the gradient it stores (speculatively: they are used only if no later
-          # contribution changes x.grad -- the first consumer in forward order is the last here)
-          bx, bmask, bmean, brstd, bact, balpha = x.bn_src
-          stats = torch.empty((bn_rows, 2, cin), dtype=torch.float32, device=ctx.device)
-          if have_prev:
-            _grad_wait(x)
-            dx = prev
-          else:
-            dx = ctx.empty(shape)
-          with _Timed('dgrad', flops, tag):
-            _chk(L.se3ds_conv2d_dgrad_bnstats(
-                dys.data_ptr(), wn.data_ptr(), dx.data_ptr(), ctx.code, n, h, w, cin, ho, wo,
-                layer.cout, k, k, s, pt, pl, 1 if wrap else 0, _lib.ptr(scale), _lib.ptr(in_mask),
-                prev.data_ptr() if have_prev else None, bx.data_ptr(), _lib.ptr(bmask),
-                bmean.data_ptr(), brstd.data_ptr(), bact, float(balpha), stats.data_ptr(),
-                _lib.stream()), 'se3ds_conv2d_dgrad_bnstats')
-          if have_prev:
-            x.gver += 1
-            _grad_mark(x)
-          else:
-            accumulate(x, dx)
-          x.bn_stats = (stats, x.gver)
-        elif have_prev:
-          # second contribution (e.g. a ResNet block's input: residual branch first, then this
-          # conv): the epilogue adds the existing gradient in place instead of a separate pass
-          _grad_wait(x)
-          with _Timed('dgrad', flops * n / xd.shape[0], tag):
-            _chk(L.se3ds_conv2d_dgrad_acc(dys.data_ptr(), wn.data_ptr(), prev.data_ptr(), ctx.code,
-                                          n, h, w, cin, ho, wo, layer.cout, k, k, s, pt, pl,
-                                          1 if wrap else 0, _lib.ptr(row_scale), _lib.ptr(scale),
-                                          None, _lib.ptr(in_mask), ACT_NONE, 0.0, prev.data_ptr(),
-                                          _lib.stream()), 'se3ds_conv2d_dgrad_acc')
-          x.gver += 1
-          _grad_mark(x)
-        else:
-          dx = ctx.empty(shape)
-          with _Timed('dgrad', flops * n / xd.shape[0], tag):
-            _chk(L.se3ds_conv2d_dgrad(dys.data_ptr(), wn.data_ptr(), dx.data_ptr(), ctx.code, n, h,
-                                      w, cin, ho, wo, layer.cout, k, k, s, pt, pl,
-                                      1 if wrap else 0, _lib.ptr(row_scale), _lib.ptr(scale), None,
-                                      _lib.ptr(in_mask), ACT_NONE, 0.0, _lib.stream()),
-                 'se3ds_conv2d_dgrad')
-          accumulate(x, dx)
-    ctx.record(bwd)
-  if partial:
-    return out, um
-  return out
+      else:
+        _chk(L.se3ds_row_scale(dy.data_ptr(), ctx.code, rows, cout, row_scale.data_ptr(),
+                               dys.data_ptr(), _lib.stream()), 'se3ds_row_scale')
+      row_scale = None
+  if ctx.param_grads:
+    _conv2d_bwd_params(sv, geo, dy, dys, row_scale, bias_done)
+  if sv.x.requires_grad:
+    _conv2d_bwd_input(sv, geo, dys, row_scale, lim)
+
+
+def _conv2d_bwd_params(sv, geo, dy, dys, row_scale, bias_done):
+  ctx, layer, L = sv.ctx, sv.layer, _L()
+  _, n, h, w, cin, ho, wo, cout, k, _, s, pt, pl, wrap = geo
+  xd, st = sv.x.data, layer.store
+  if layer.has_bias and not bias_done:
+    _colsum(ctx, dy.data_ptr(), ctx.code, n * ho * wo, cout,
+            row_scale=sv.bu if sv.partial else None, out=st.grad_views[layer.name + '/bias'])
+  ptrs = (xd.data_ptr(), dys.data_ptr(), st.grad_views[layer.name + '/kernel'].data_ptr())
+  if (cout <= 16 and cin > 16 and s == 1 and ho == h and wo == w and pt == pl and not wrap and
+      not sv.partial):
+    # thin outputs, the 128->3 / 128->1 convs: role-swapped weight gradient (x streamed once)
+    wsz = L.se3ds_conv2d_wgrad_swapped_workspace_bytes(n, h, w, cin, cout, k)
+    ws = _global_ws(ctx.device, 'wgrad', wsz)
+    with _Timed('wgrad', sv.flops, sv.tag):
+      _chk(L.se3ds_conv2d_wgrad_swapped(*ptrs, ctx.code, n, h, w, cin, cout, k, pt, 0, ws.data_ptr(),
+                                        ws.numel(), _lib.stream()), 'se3ds_conv2d_wgrad_swapped')
+  else:
+    wsz = L.se3ds_conv2d_wgrad_workspace_bytes(n, ho, wo, cin, cout, k, k)
+    with _Timed('wgrad', sv.flops, sv.tag):
+      _wgrad(ctx, layer, (*ptrs, *geo, _lib.ptr(sv.in_mask), 1 if ctx.binary_masks else 0,
+                          _lib.ptr(row_scale)), wsz)
+
+
+def _conv2d_bwd_input(sv, geo, dys, row_scale, lim):
+  ctx, x, xd, n, L = sv.ctx, sv.x, sv.x.data, geo.n, _L()
+  prev = x.grad
+  shape = (n,) + tuple(xd.shape[1:])
+  have_prev = prev is not None and tuple(prev.shape) == shape and prev.dtype == xd.dtype
+  bn_rows = 0
+  if (x.bn_src is not None and row_scale is None and lim is None and _FUSED_BN_BWD and
+      (prev is None or have_prev)):
+    bn_rows = int(L.se3ds_conv2d_dgrad_bnstats_rows(ctx.code, n, geo.h, geo.w, geo.cin, geo.cout,
+                                                    geo.kh, geo.kw, geo.stride, 0))
+  if bn_rows > 0:
+    stats = torch.empty((bn_rows, 2, geo.cin), dtype=torch.float32, device=ctx.device)
+  if have_prev:
+    # second contribution (e.g. a ResNet block's input: residual branch first, then this
+    # conv): the epilogue adds the existing gradient in place instead of a separate pass
+    _grad_wait(x)
+    dx = prev
+  else:
+    dx = ctx.empty(shape)
+  args = (dys.data_ptr(), sv.wn.data_ptr(), dx.data_ptr(), *geo)
+  tail = (_lib.ptr(row_scale), _lib.ptr(sv.scale), None, _lib.ptr(sv.in_mask), ACT_NONE, 0.0)
+  with _Timed('dgrad', sv.flops if bn_rows > 0 else sv.flops * n / xd.shape[0], sv.tag):
+    if bn_rows > 0:
+      # x is a batch norm's output: this data gradient also takes the norm's backward
+      # statistics from the gradient it stores (speculatively: they are used only if no later
+      # contribution changes x.grad -- the first consumer in forward order is the last here)
+      bn = x.bn_src
+      _chk(L.se3ds_conv2d_dgrad_bnstats(
+          *args, _lib.ptr(sv.scale), _lib.ptr(sv.in_mask), prev.data_ptr() if have_prev else None,
+          bn.x.data_ptr(), _lib.ptr(bn.amask), bn.mean.data_ptr(), bn.rstd.data_ptr(), bn.act,
+          float(bn.alpha), stats.data_ptr(), _lib.stream()), 'se3ds_conv2d_dgrad_bnstats')
+    elif have_prev:
+      _chk(L.se3ds_conv2d_dgrad_acc(*args, *tail, prev.data_ptr(), _lib.stream()),
+           'se3ds_conv2d_dgrad_acc')
+    else:
+      _chk(L.se3ds_conv2d_dgrad(*args, *tail, _lib.stream()), 'se3ds_conv2d_dgrad')
+  if have_prev:
+    x.gver += 1
+    _grad_mark(x)
+  else:
+    accumulate(x, dx)
+  if bn_rows > 0:
+    x.bn_stats = BnStats(stats, x.gver)
 
 
 def conv_transpose2d(ctx: Ctx, x: Var, layer: ConvLayer):
@@ -1253,6 +1260,7 @@ def conv_transpose2d(ctx: Ctx, x: Var, layer: ConvLayer):
   assert cin_t == layer.cin
   k = layer.k
   H, W = 2 * hi, 2 * wi          # the associated forward conv maps (H,W,cout_T) -> (hi,wi,cin_T)
+  geo = _Geom(ctx.code, n, H, W, layer.cout, hi, wi, cin_t, k, k, 2, 0, 0, 0)
   L = _L()
   wt, wn = layer.operands(ctx)   # kernel (k,k,cout_T,cin_T) == HWIO of the associated conv
   y = ctx.empty((n, H, W, layer.cout))
@@ -1267,8 +1275,7 @@ def conv_transpose2d(ctx: Ctx, x: Var, layer: ConvLayer):
                                          wi, cin_t, layer.cout, _lib.ptr(bias), _lib.stream()),
            'se3ds_conv_transpose2x2_fwd')
     else:
-      _chk(L.se3ds_conv2d_dgrad(xd.data_ptr(), wn.data_ptr(), y.data_ptr(), ctx.code, n, H, W,
-                                layer.cout, hi, wi, cin_t, k, k, 2, 0, 0, 0, None, None,
+      _chk(L.se3ds_conv2d_dgrad(xd.data_ptr(), wn.data_ptr(), y.data_ptr(), *geo, None, None,
                                 _lib.ptr(bias), None, ACT_NONE, 0.0, _lib.stream()),
            'se3ds_conv2d_dgrad')
   out = Var(y)
@@ -1278,22 +1285,19 @@ def conv_transpose2d(ctx: Ctx, x: Var, layer: ConvLayer):
       out.grad = None
       if dy is None:
         return
-      st = layer.store
       if ctx.param_grads:
         if bias is not None:
           _colsum(ctx, dy.data_ptr(), ctx.code, n * H * W, layer.cout,
-                  out=st.grad_views[layer.name + '/bias'])
+                  out=layer.store.grad_views[layer.name + '/bias'])
         wsz = L.se3ds_conv2d_wgrad_workspace_bytes(n, hi, wi, layer.cout, cin_t, k, k)
-        gk = st.grad_views[layer.name + '/kernel']
+        gk = layer.store.grad_views[layer.name + '/kernel']
         with _Timed('convT_wgrad', flops, tag):
-          _wgrad(ctx, layer, (dy.data_ptr(), xd.data_ptr(), gk.data_ptr(), ctx.code, n, H, W,
-                              layer.cout, hi, wi, cin_t, k, k, 2, 0, 0, 0, None, 0, None), wsz)
+          _wgrad(ctx, layer, (dy.data_ptr(), xd.data_ptr(), gk.data_ptr(), *geo, None, 0, None), wsz)
       if x.requires_grad:
         dx = ctx.empty(xd.shape)
         with _Timed('convT_dgrad', flops, tag):
-          _chk(L.se3ds_conv2d_fwd(dy.data_ptr(), wt.data_ptr(), dx.data_ptr(), ctx.code, n, H, W,
-                                  layer.cout, hi, wi, cin_t, k, k, 2, 0, 0, 0, None, 0, None, None,
-                                  None, None, ACT_NONE, 0.0, _lib.stream()), 'se3ds_conv2d_fwd')
+          _chk(L.se3ds_conv2d_fwd(dy.data_ptr(), wt.data_ptr(), dx.data_ptr(), *geo, None, 0, None,
+                                  None, None, None, ACT_NONE, 0.0, _lib.stream()), 'se3ds_conv2d_fwd')
         accumulate(x, dx)
     ctx.record(bwd)
   return out
@@ -1310,6 +1314,7 @@ class NormLayer:
     if kind == 'batch':
       store.add(name + '/moving_mean', (c,), zeros_init, trainable=False)
       store.add(name + '/moving_variance', (c,), ones_init, trainable=False)
+    self._cg_colpart = None   # bias partials of the channel-group backward (_norm_bwd_cg)
 
 
 _NORM_DEBUG = {} if os.environ.get('SE3DS_NORM_DEBUG') else None
@@ -1336,50 +1341,37 @@ _MASK_CACHE = os.environ.get('SE3DS_MASK_CACHE', '1') != '0'
 _DROP_1X1_MASK = os.environ.get('SE3DS_DROP_1X1_MASK', '1') != '0'
 
 
-def norm_act(ctx: Ctx, x: Var, layer: NormLayer, act=ACT_NONE, alpha=0.0, res: Var = None,
-             post: Var = None, in_act=None) -> Var:
-  """y = act(norm(x) [+ res]) [+ post].  Batch norm uses cross-replica batch statistics when
-  training (SyncBatchNormalization) and moving statistics otherwise.  in_act = (act, alpha):
-  x is the output of a conv with that fused activation and this norm is its ONLY consumer; the
-  backward then applies the activation derivative itself (it reads x anyway) and the conv skips
-  its separate derivative pass."""
-  xd = x.data
-  n, h, w, c = xd.shape
-  st = layer.store
-  L = _L()
-  inst = layer.kind == 'instance'
-  g = n if inst else 1
-  r = h * w if inst else n * h * w
-  eps = IN_EPS if inst else BN_EPS
-  gamma, beta = st[layer.name + '/gamma'], st[layer.name + '/beta']
-  use_moving = (not inst) and (not ctx.training or getattr(ctx, 'bn_use_moving', False))
+def _norm_debug(who, xd, layer):   # SE3DS_NORM_DEBUG counters; who: the layer's name or a route
+  if _NORM_DEBUG is not None:
+    key = (who, tuple(xd.shape), layer.kind)
+    _NORM_DEBUG[key] = _NORM_DEBUG.get(key, 0) + 1
+
+
+def _norm_stats(ctx, x, layer, g, r, c, use_moving):
+  """(scale, shift, mean, rstd, count) from the moving statistics, the producing conv's column sums
+  (x.col_stats) or the op's own pass over x; several replicas all-reduce the sums."""
+  st, L, inst = layer.store, _L(), layer.kind == 'instance'
   scale = torch.empty((g, c), dtype=torch.float32, device=ctx.device)
-  shift = torch.empty_like(scale)
-  mean = torch.empty_like(scale)
-  rstd = torch.empty_like(scale)
+  shift, mean, rstd = torch.empty_like(scale), torch.empty_like(scale), torch.empty_like(scale)
   count = float(r)
+  affine = (st[layer.name + '/gamma'].data_ptr(), st[layer.name + '/beta'].data_ptr(),
+            IN_EPS if inst else BN_EPS, BN_MOMENTUM)
+  mm = st[layer.name + '/moving_mean'] if not inst else None
+  mv = st[layer.name + '/moving_variance'] if not inst else None
+  outs = (scale.data_ptr(), shift.data_ptr(), mean.data_ptr(), rstd.data_ptr(), _lib.stream())
+  fused = x.col_stats   # statistics out of the producing convolution's epilogue, if they fit
+  fused = fused if fused is not None and not inst and fused.shape[2] == c else None
   if use_moving:
-    _chk(L.se3ds_norm_finalize(None, 1.0, g, c, gamma.data_ptr(), beta.data_ptr(), eps,
-                               BN_MOMENTUM, st[layer.name + '/moving_mean'].data_ptr(),
-                               st[layer.name + '/moving_variance'].data_ptr(), 1,
-                               scale.data_ptr(), shift.data_ptr(), mean.data_ptr(),
-                               rstd.data_ptr(), _lib.stream()), 'se3ds_norm_finalize')
+    _chk(L.se3ds_norm_finalize(None, 1.0, g, c, *affine, mm.data_ptr(), mv.data_ptr(), 1, *outs),
+         'se3ds_norm_finalize')
+  elif fused is not None and ctx.world == 1 and fused.shape[0] <= 2048:
+    # single replica: column reduction and finalize in one launch
+    _chk(L.se3ds_norm_reduce_rows_finalize(fused.data_ptr(), fused.shape[0], c, count, *affine,
+                                           mm.data_ptr(), mv.data_ptr(), *outs),
+         'se3ds_norm_reduce_rows_finalize')
+    x.col_stats = None
   else:
-    fused = getattr(x, 'col_stats', None)
-    finalized = False
-    if (fused is not None and not inst and fused.shape[2] == c and ctx.world == 1 and
-        fused.shape[0] <= 2048):
-      # statistics came out of the producing convolution's epilogue; single replica: column
-      # reduction and finalize in one launch
-      _chk(L.se3ds_norm_reduce_rows_finalize(
-          fused.data_ptr(), fused.shape[0], c, count, gamma.data_ptr(), beta.data_ptr(), eps,
-          BN_MOMENTUM, st[layer.name + '/moving_mean'].data_ptr(),
-          st[layer.name + '/moving_variance'].data_ptr(), scale.data_ptr(), shift.data_ptr(),
-          mean.data_ptr(), rstd.data_ptr(), _lib.stream()), 'se3ds_norm_reduce_rows_finalize')
-      x.col_stats = None
-      finalized = True
-    elif fused is not None and not inst and fused.shape[2] == c:
-      # statistics came out of the producing convolution's epilogue
+    if fused is not None:
       sums = torch.empty((1, 2, c), dtype=torch.float32, device=ctx.device)
       ws = ctx.ws('norm', L.se3ds_norm_workspace_bytes(max(1, (fused.shape[0] + 511) // 512), c))
       _chk(L.se3ds_norm_reduce_rows(fused.data_ptr(), fused.shape[0], c, sums.data_ptr(),
@@ -1387,197 +1379,205 @@ def norm_act(ctx: Ctx, x: Var, layer: NormLayer, act=ACT_NONE, alpha=0.0, res: V
            'se3ds_norm_reduce_rows')
       x.col_stats = None
     else:
-      if _NORM_DEBUG is not None:   # SE3DS_NORM_DEBUG: which norms take their own statistics pass
-        key = (layer.name, tuple(xd.shape), layer.kind)
-        _NORM_DEBUG[key] = _NORM_DEBUG.get(key, 0) + 1
-      sums = _colsum(ctx, xd.data_ptr(), ctx.code, r, c, groups=g)
-    if not finalized:
-      if not inst and ctx.world > 1:
-        ctx.allreduce_sum(sums)
-        count = float(r * ctx.world)
-      mm = st[layer.name + '/moving_mean'] if not inst else None
-      mv = st[layer.name + '/moving_variance'] if not inst else None
-      _chk(L.se3ds_norm_finalize(sums.data_ptr(), count, g, c, gamma.data_ptr(), beta.data_ptr(),
-                                 eps, BN_MOMENTUM, _lib.ptr(mm), _lib.ptr(mv), 0, scale.data_ptr(),
-                                 shift.data_ptr(), mean.data_ptr(), rstd.data_ptr(), _lib.stream()),
-           'se3ds_norm_finalize')
+      _norm_debug(layer.name, x.data, layer)   # which norms take their own statistics pass
+      sums = _colsum(ctx, x.data.data_ptr(), ctx.code, r, c, groups=g)
+    if not inst and ctx.world > 1:
+      ctx.allreduce_sum(sums)
+      count = float(r * ctx.world)
+    _chk(L.se3ds_norm_finalize(sums.data_ptr(), count, g, c, *affine, _lib.ptr(mm), _lib.ptr(mv), 0,
+                               *outs), 'se3ds_norm_finalize')
+  return scale, shift, mean, rstd, count
+
+
+def norm_act(ctx: Ctx, x: Var, layer: NormLayer, act=ACT_NONE, alpha=0.0, res: Var = None,
+             post: Var = None, in_act=None) -> Var:
+  """y = act(norm(x) [+ res]) [+ post].  Batch norm uses cross-replica batch statistics when
+  training (SyncBatchNormalization) and moving statistics otherwise.  in_act = (act, alpha):
+  x is the output of a conv with that fused activation and this norm is its ONLY consumer; the
+  backward then applies the activation derivative itself (it reads x anyway) and the conv skips
+  its separate derivative pass."""
+  xd, inst = x.data, layer.kind == 'instance'
+  n, h, w, c = xd.shape
+  g, r = (n, h * w) if inst else (1, n * h * w)
+  use_moving = (not inst) and (not ctx.training or ctx.bn_use_moving)
+  scale, shift, mean, rstd, count = _norm_stats(ctx, x, layer, g, r, c, use_moving)
   y = ctx.empty(xd.shape)
   # one "output > 0" bit per element for the backward pass (instead of re-reading y twice)
   amask = None
   if (ctx.tape is not None and act != ACT_NONE and post is None and c % 8 == 0 and
       xd.dtype == torch.bfloat16):
     amask = torch.empty(xd.numel() // 8, dtype=torch.uint8, device=ctx.device)
-  _chk(L.se3ds_norm_apply(xd.data_ptr(), ctx.code, g, r, c, scale.data_ptr(), shift.data_ptr(),
-                          _lib.ptr(res.data if res is not None else None),
-                          _lib.ptr(post.data if post is not None else None), act, float(alpha),
-                          y.data_ptr(), _lib.ptr(amask), _lib.stream()), 'se3ds_norm_apply')
+  _chk(_L().se3ds_norm_apply(xd.data_ptr(), ctx.code, g, r, c, scale.data_ptr(), shift.data_ptr(),
+                             _lib.ptr(res.data if res is not None else None),
+                             _lib.ptr(post.data if post is not None else None), act, float(alpha),
+                             y.data_ptr(), _lib.ptr(amask), _lib.stream()), 'se3ds_norm_apply')
   out = Var(y)
   if act != ACT_NONE and ctx.act_taps is not None:
     ctx.act_taps[layer.name] = y
   if (ctx.tape is not None and not inst and not use_moving and post is None and c % 8 == 0 and
       xd.dtype == torch.bfloat16 and (act == ACT_NONE or amask is not None)):
-    out.bn_src = (xd, amask, mean, rstd, act, alpha)   # a consuming conv's data gradient may fuse
+    out.bn_src = BnSrc(xd, amask, mean, rstd, act, alpha)   # a consuming conv's data gradient may fuse
   sync_bwd = (not inst) and ctx.world > 1 and not use_moving   # the backward all-reduces too
   if ctx.tape is not None:
-    def bwd(g=g):
-      dy = out.grad
-      fused = out.bn_stats
-      if fused is not None and fused[1] != out.gver:
-        fused = None   # the gradient changed after the epilogue that took the statistics
-      out.bn_stats = None
-      out.grad = None
-      if dy is None:
-        if sync_bwd:
-          # no gradient reaches this norm on this replica / branch: its statistics gradients are
-          # zero, but the collective (and a paired twin parked in allreduce_then) still needs us
-          ctx.allreduce_then(torch.zeros((g, 2, c), dtype=torch.float32, device=ctx.device),
-                             lambda: None)
-        return
-      if post is not None:
-        # y = act(.) + post: the activation mask must come from (y - post); recompute it
-        raise NotImplementedError
-      lim = getattr(ctx, 'batch_limit', None)
-      shape = xd.shape
-      if lim is not None and lim < n:
-        # per-sample statistics only (instance norm): the first `lim` groups are a prefix of
-        # every buffer involved
-        assert inst and dy.shape[0] == lim and not ctx.param_grads
-        g = lim
-        shape = (lim,) + tuple(xd.shape[1:])
-      ws = ctx.ws('norm', L.se3ds_norm_workspace_bytes(g, c))
-      want_res = res is not None and res.requires_grad
-      dres = ctx.empty(shape) if want_res else None
-      dx = ctx.empty(shape)
-      if use_moving:
-        if ctx.param_grads:
-          bs = torch.empty((g, 2, c), dtype=torch.float32, device=ctx.device)
-          _chk(L.se3ds_norm_bwd_stats(dy.data_ptr(), y.data_ptr(), xd.data_ptr(), ctx.code, g, r,
-                                      c, mean.data_ptr(), rstd.data_ptr(), act, float(alpha),
-                                      bs.data_ptr(), st.grad_views[layer.name + '/beta'].data_ptr(),
-                                      st.grad_views[layer.name + '/gamma'].data_ptr(),
-                                      _lib.ptr(amask), ws.data_ptr(), ws.numel(), _lib.stream()),
-               'se3ds_norm_bwd_stats')
-        _chk(L.se3ds_affine_bwd(dy.data_ptr(), y.data_ptr(), ctx.code, g, r, c, scale.data_ptr(),
-                                act, float(alpha), dx.data_ptr(), _lib.ptr(dres), _lib.ptr(amask),
-                                _lib.stream()), 'se3ds_affine_bwd')
-      else:
-        in_a = in_act[0] if in_act else 0
-        if (_NORM_CG and not sync_bwd and g == 1 and fused is None and lim is None and
-            L.se3ds_norm_bwd_cg_supported(ctx.code, r, c, act, 1 if amask is not None else 0, in_a)):
-          # Round 5: statistics partials + apply in the channel-group layout, the apply workgroups
-          # fold the partial rows themselves -- no stand-alone column reduction between the passes
-          # (se3ds_norm_bwd_cg); beta / gamma gradients are written by the apply kernel
-          sink = x.row_sink
-          use_rows = (sink is not None and _FUSED_ROW_SCALE and ctx.param_grads and not in_act and
-                      x.grad is None)
-          cws = ctx.ws('norm_cg', L.se3ds_norm_bwd_cg_workspace_bytes(c))
-          colpart, nrows = None, 0
-          if use_rows:
-            # (the bias partials must outlive the module's deferred reduction: the layer's own)
-            nrows = int(L.se3ds_norm_bwd_cg_col_rows(r, c))
-            colpart = layer.__dict__.get('_cg_colpart')
-            if colpart is None or colpart.numel() < nrows * c:
-              colpart = torch.empty(nrows * c, dtype=torch.float32, device=ctx.device)
-              layer._cg_colpart = colpart
-          pg = ctx.param_grads
-          _chk(L.se3ds_norm_bwd_cg(
-              dy.data_ptr(), xd.data_ptr(), ctx.code, r, c, mean.data_ptr(), rstd.data_ptr(),
-              gamma.data_ptr(), count, act, float(alpha), dx.data_ptr(), _lib.ptr(dres),
-              _lib.ptr(amask), in_a, float(in_act[1]) if in_act else 0.0,
-              st.grad_views[layer.name + '/beta'].data_ptr() if pg else None,
-              st.grad_views[layer.name + '/gamma'].data_ptr() if pg else None, None,
-              sink[1].data_ptr() if use_rows else None, sink[0].data_ptr() if use_rows else None,
-              _lib.ptr(colpart), cws.data_ptr(), cws.numel(), _lib.stream()), 'se3ds_norm_bwd_cg')
-          if _NORM_DEBUG is not None:
-            for k in (('cg', tuple(xd.shape), layer.kind),) + (
-                (('fused-rows', tuple(xd.shape), layer.kind),) if use_rows else ()):
-              _NORM_DEBUG[k] = _NORM_DEBUG.get(k, 0) + 1
-          if use_rows:
-            reduce_or_defer(ctx, (colpart.data_ptr(), nrows, c // 4,
-                                  sink[2].grad_views[sink[3]].data_ptr()))
-          if in_act:
-            x.grad_pre_act = True
-          accumulate(x, dx)
-          if use_rows:
-            x.grad_scaled = x.gver
-          if want_res:
-            accumulate(res, dres)
-          return
-        bs = torch.empty((g, 2, c), dtype=torch.float32, device=ctx.device)
-        direct = ctx.param_grads and g == 1
-        # parameter gradients are the LOCAL sums (aggregated later with every other gradient);
-        # for batch norm the reduction writes them straight into the gradient arena
-        if fused is not None and g == 1 and fused[0].shape[2] == c:
-          # the statistics came out of the data-gradient epilogue that produced dy
-          rows = fused[0].shape[0]
-          rws = ctx.ws('norm', L.se3ds_norm_workspace_bytes(max(1, (rows + 511) // 512), c))
-          _chk(L.se3ds_norm_reduce_rows_dst(
-              fused[0].data_ptr(), rows, c, bs.data_ptr(),
-              st.grad_views[layer.name + '/beta'].data_ptr() if direct else None,
-              st.grad_views[layer.name + '/gamma'].data_ptr() if direct else None,
-              rws.data_ptr(), rws.numel(), _lib.stream()), 'se3ds_norm_reduce_rows_dst')
-          if _NORM_DEBUG is not None:
-            _NORM_DEBUG[('fused-bwd', tuple(xd.shape), layer.kind)] = \
-                _NORM_DEBUG.get(('fused-bwd', tuple(xd.shape), layer.kind), 0) + 1
-        else:
-          _chk(L.se3ds_norm_bwd_stats(
-              dy.data_ptr(), y.data_ptr(), xd.data_ptr(), ctx.code, g, r, c, mean.data_ptr(),
-              rstd.data_ptr(), act, float(alpha), bs.data_ptr(),
-              st.grad_views[layer.name + '/beta'].data_ptr() if direct else None,
-              st.grad_views[layer.name + '/gamma'].data_ptr() if direct else None,
-              _lib.ptr(amask), ws.data_ptr(), ws.numel(), _lib.stream()), 'se3ds_norm_bwd_stats')
-        if not ctx.param_grads or direct:
-          pass
-        else:
-          tot = _colsum(ctx, bs.data_ptr(), _lib.F32, g, 2 * c)
-          st.grad_views[layer.name + '/beta'].copy_(tot[0, 0, :c])
-          st.grad_views[layer.name + '/gamma'].copy_(tot[0, 0, c:])
-
-        def finish():
-          sink = x.row_sink
-          rows_done = False
-          if (sink is not None and _FUSED_ROW_SCALE and ctx.param_grads and g == 1 and not in_act and
-              x.grad is None and lim is None and xd.dtype == torch.bfloat16):
-            # x is the output of a biased partial conv and this norm (so far) its only consumer:
-            # store dx pre-scaled for that conv's backward pass and write its bias gradient here
-            cws = ctx.ws('norm_rows', L.se3ds_norm_workspace_bytes(3, c))
-            rc = L.se3ds_norm_bwd_apply_rows(
-                dy.data_ptr(), xd.data_ptr(), ctx.code, r, c, mean.data_ptr(), rstd.data_ptr(),
-                gamma.data_ptr(), bs.data_ptr(), count, act, float(alpha), dx.data_ptr(),
-                _lib.ptr(dres), _lib.ptr(amask), sink[1].data_ptr(), sink[0].data_ptr(),
-                sink[2].grad_views[sink[3]].data_ptr(), cws.data_ptr(), cws.numel(), _lib.stream())
-            if rc == 0:
-              rows_done = True
-              if _NORM_DEBUG is not None:
-                _NORM_DEBUG[('fused-rows', tuple(xd.shape), layer.kind)] = \
-                    _NORM_DEBUG.get(('fused-rows', tuple(xd.shape), layer.kind), 0) + 1
-            elif rc not in (-5, -3):   # SE3DS_E_UNSUPPORTED / SE3DS_E_WORKSPACE: separate passes
-              _chk(rc, 'se3ds_norm_bwd_apply_rows')
-          if not rows_done:
-            _chk(L.se3ds_norm_bwd_apply(dy.data_ptr(), y.data_ptr(), xd.data_ptr(), ctx.code, g, r,
-                                        c, mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(),
-                                        bs.data_ptr(), count, act, float(alpha), dx.data_ptr(),
-                                        _lib.ptr(dres), _lib.ptr(amask),
-                                        in_act[0] if in_act else 0,
-                                        float(in_act[1]) if in_act else 0.0,
-                                        _lib.stream()), 'se3ds_norm_bwd_apply')
-          if in_act:
-            x.grad_pre_act = True
-          accumulate(x, dx)
-          if rows_done:
-            x.grad_scaled = x.gver
-          if want_res:
-            accumulate(res, dres)
-        if sync_bwd:
-          ctx.allreduce_then(bs, finish)   # SyncBN backward: statistics gradients are global
-        else:
-          finish()
-        return
-      accumulate(x, dx)
-      if want_res:
-        accumulate(res, dres)
-    ctx.record(bwd, sync=sync_bwd)
+    sv = SimpleNamespace(ctx=ctx, x=x, out=out, layer=layer, res=res, post=post, act=act,
+                         alpha=float(alpha), in_act=in_act, amask=amask, scale=scale, mean=mean,
+                         rstd=rstd, gamma=layer.store[layer.name + '/gamma'], count=count, g=g, r=r,
+                         c=c, use_moving=use_moving, sync_bwd=sync_bwd)
+    ctx.record(lambda: _norm_bwd(sv), sync=sync_bwd)   # (the tape keeps sv's tensors alive)
   return out
+
+
+def _norm_bwd(sv):
+  ctx, out, xd, c, L = sv.ctx, sv.out, sv.x.data, sv.c, _L()
+  dy = out.grad
+  fused = out.take_bn_stats()   # rows a data-gradient epilogue took from exactly this gradient
+  out.grad = None
+  if dy is None:
+    if sv.sync_bwd:
+      # no gradient reaches this norm on this replica / branch: its statistics gradients are
+      # zero, but the collective (and a paired twin parked in allreduce_then) still needs us
+      ctx.allreduce_then(torch.zeros((sv.g, 2, c), dtype=torch.float32, device=ctx.device),
+                         lambda: None)
+    return
+  if sv.post is not None:
+    # y = act(.) + post: the activation mask must come from (y - post); recompute it
+    raise NotImplementedError
+  lim = ctx.batch_limit
+  g, shape = sv.g, xd.shape
+  if lim is not None and lim < xd.shape[0]:
+    # per-sample statistics only (instance norm): the first `lim` groups are a prefix of
+    # every buffer involved
+    assert sv.layer.kind == 'instance' and dy.shape[0] == lim and not ctx.param_grads
+    g, shape = lim, (lim,) + tuple(xd.shape[1:])
+  ws = ctx.ws('norm', L.se3ds_norm_workspace_bytes(g, c))
+  dres = ctx.empty(shape) if sv.res is not None and sv.res.requires_grad else None
+  dx = ctx.empty(shape)
+  if sv.use_moving:
+    _norm_bwd_moving(sv, dy, dx, dres, g, ws)
+  elif (_NORM_CG and not sv.sync_bwd and g == 1 and fused is None and lim is None and
+        L.se3ds_norm_bwd_cg_supported(ctx.code, sv.r, c, sv.act, 1 if sv.amask is not None else 0,
+                                      sv.in_act[0] if sv.in_act else 0)):
+    _norm_bwd_cg(sv, dy, dx, dres)
+  else:
+    _norm_bwd_split(sv, dy, dx, dres, g, ws, fused, lim)
+
+
+def _norm_deliver(sv, dx, dres, pre_act, scaled=False):
+  # pre_act / scaled: dx carries the activation derivative / row scale of the conv that produced x
+  if pre_act:
+    sv.x.grad_pre_act = True
+  accumulate(sv.x, dx)
+  if scaled:
+    sv.x.grad_scaled = sv.x.gver
+  if dres is not None:
+    accumulate(sv.res, dres)
+
+
+def _norm_bwd_sums(sv, dy, g, ws, fused):
+  """bs [g][2][c], the backward statistics (= the beta / gamma gradients): from the rows `fused` of
+  the data gradient that produced dy, or from a pass over dy and x."""
+  ctx, xd, c, L = sv.ctx, sv.x.data, sv.c, _L()
+  bs = torch.empty((g, 2, c), dtype=torch.float32, device=ctx.device)
+  # parameter gradients are the LOCAL sums (aggregated later with every other gradient);
+  # for batch norm the reduction writes them straight into the gradient arena
+  direct = ctx.param_grads and g == 1
+  gv, name = sv.layer.store.grad_views, sv.layer.name   # (lazy: the first touch allocates the arena)
+  dst = lambda which: gv[name + which].data_ptr() if direct else None
+  if fused is not None and g == 1 and fused.shape[2] == c:
+    rows = fused.shape[0]
+    rws = ctx.ws('norm', L.se3ds_norm_workspace_bytes(max(1, (rows + 511) // 512), c))
+    _chk(L.se3ds_norm_reduce_rows_dst(fused.data_ptr(), rows, c, bs.data_ptr(), dst('/beta'),
+                                      dst('/gamma'), rws.data_ptr(), rws.numel(), _lib.stream()),
+         'se3ds_norm_reduce_rows_dst')
+    _norm_debug('fused-bwd', xd, sv.layer)
+  else:
+    _chk(L.se3ds_norm_bwd_stats(
+        dy.data_ptr(), sv.out.data.data_ptr(), xd.data_ptr(), ctx.code, g, sv.r, c,
+        sv.mean.data_ptr(), sv.rstd.data_ptr(), sv.act, sv.alpha, bs.data_ptr(), dst('/beta'),
+        dst('/gamma'), _lib.ptr(sv.amask), ws.data_ptr(), ws.numel(), _lib.stream()),
+         'se3ds_norm_bwd_stats')
+  if ctx.param_grads and not direct:
+    tot = _colsum(ctx, bs.data_ptr(), _lib.F32, g, 2 * c)
+    gv[name + '/beta'].copy_(tot[0, 0, :c])
+    gv[name + '/gamma'].copy_(tot[0, 0, c:])
+  return bs
+
+
+def _norm_bwd_moving(sv, dy, dx, dres, g, ws):
+  ctx = sv.ctx   # (moving statistics: the norm is an affine map of x)
+  if ctx.param_grads:
+    _norm_bwd_sums(sv, dy, g, ws, None)
+  _chk(_L().se3ds_affine_bwd(dy.data_ptr(), sv.out.data.data_ptr(), ctx.code, g, sv.r, sv.c,
+                             sv.scale.data_ptr(), sv.act, sv.alpha, dx.data_ptr(), _lib.ptr(dres),
+                             _lib.ptr(sv.amask), _lib.stream()), 'se3ds_affine_bwd')
+  _norm_deliver(sv, dx, dres, False)
+
+
+def _norm_bwd_cg(sv, dy, dx, dres):
+  """Round 5: statistics partials + apply in the channel-group layout, the apply workgroups fold the
+  partial rows themselves (no column reduction in between) and write the beta / gamma gradients."""
+  ctx, x, layer, r, c, L = sv.ctx, sv.x, sv.layer, sv.r, sv.c, _L()
+  sink = x.row_sink
+  use_rows = (sink is not None and _FUSED_ROW_SCALE and ctx.param_grads and not sv.in_act and
+              x.grad is None)
+  cws = ctx.ws('norm_cg', L.se3ds_norm_bwd_cg_workspace_bytes(c))
+  colpart, nrows = None, 0
+  if use_rows:
+    # (the bias partials must outlive the module's deferred reduction: the layer's own)
+    nrows = int(L.se3ds_norm_bwd_cg_col_rows(r, c))
+    colpart = layer._cg_colpart
+    if colpart is None or colpart.numel() < nrows * c:
+      colpart = layer._cg_colpart = torch.empty(nrows * c, dtype=torch.float32, device=ctx.device)
+  gv, pg = layer.store.grad_views, ctx.param_grads
+  in_a, in_alpha = sv.in_act or (0, 0.0)
+  _chk(L.se3ds_norm_bwd_cg(
+      dy.data_ptr(), x.data.data_ptr(), ctx.code, r, c, sv.mean.data_ptr(), sv.rstd.data_ptr(),
+      sv.gamma.data_ptr(), sv.count, sv.act, sv.alpha, dx.data_ptr(), _lib.ptr(dres),
+      _lib.ptr(sv.amask), in_a, float(in_alpha),
+      gv[layer.name + '/beta'].data_ptr() if pg else None,
+      gv[layer.name + '/gamma'].data_ptr() if pg else None, None,
+      sink.bias_scale.data_ptr() if use_rows else None,
+      sink.out_scale.data_ptr() if use_rows else None, _lib.ptr(colpart), cws.data_ptr(),
+      cws.numel(), _lib.stream()), 'se3ds_norm_bwd_cg')
+  _norm_debug('cg', x.data, layer)
+  if use_rows:
+    _norm_debug('fused-rows', x.data, layer)
+    reduce_or_defer(ctx, (colpart.data_ptr(), nrows, c // 4, sink.bias_grad().data_ptr()))
+  _norm_deliver(sv, dx, dres, bool(sv.in_act), scaled=use_rows)
+
+
+def _norm_bwd_split(sv, dy, dx, dres, g, ws, fused, lim):
+  """Statistics, the replicas' all-reduce, then the apply pass (for a RowSink: se3ds_norm_bwd_apply_rows)."""
+  ctx, x, xd, c, L = sv.ctx, sv.x, sv.x.data, sv.c, _L()
+  bs = _norm_bwd_sums(sv, dy, g, ws, fused)
+  shared = (sv.r, c, sv.mean.data_ptr(), sv.rstd.data_ptr(), sv.gamma.data_ptr(), bs.data_ptr(),
+            sv.count, sv.act, sv.alpha, dx.data_ptr(), _lib.ptr(dres), _lib.ptr(sv.amask))
+
+  def finish():
+    sink, rc = x.row_sink, -5
+    if (sink is not None and _FUSED_ROW_SCALE and ctx.param_grads and g == 1 and not sv.in_act and
+        x.grad is None and lim is None and xd.dtype == torch.bfloat16):
+      # x is the output of a biased partial conv and this norm (so far) its only consumer:
+      # store dx pre-scaled for that conv's backward pass and write its bias gradient here
+      cws = ctx.ws('norm_rows', L.se3ds_norm_workspace_bytes(3, c))
+      rc = L.se3ds_norm_bwd_apply_rows(
+          dy.data_ptr(), xd.data_ptr(), ctx.code, *shared, sink.bias_scale.data_ptr(),
+          sink.out_scale.data_ptr(), sink.bias_grad().data_ptr(), cws.data_ptr(), cws.numel(),
+          _lib.stream())
+      if rc == 0:
+        _norm_debug('fused-rows', xd, sv.layer)
+      elif rc not in (-5, -3):   # SE3DS_E_UNSUPPORTED / SE3DS_E_WORKSPACE: separate passes
+        _chk(rc, 'se3ds_norm_bwd_apply_rows')
+    if rc != 0:
+      in_a, in_alpha = sv.in_act or (0, 0.0)
+      _chk(L.se3ds_norm_bwd_apply(dy.data_ptr(), sv.out.data.data_ptr(), xd.data_ptr(), ctx.code,
+                                  g, *shared, in_a, float(in_alpha), _lib.stream()),
+           'se3ds_norm_bwd_apply')
+    _norm_deliver(sv, dx, dres, bool(sv.in_act), scaled=rc == 0)
+  if sv.sync_bwd:
+    ctx.allreduce_then(bs, finish)   # SyncBN backward: statistics gradients are global
+  else:
+    finish()
 
 
 def add(ctx: Ctx, a: Var, b: Var) -> Var:
@@ -1650,7 +1650,7 @@ def avgpool3s2(ctx: Ctx, x: Var) -> Var:
       out.grad = None
       if dy is None or not x.requires_grad:
         return
-      lim = getattr(ctx, 'batch_limit', None)
+      lim = ctx.batch_limit
       if lim is not None and lim < n:
         assert dy.shape[0] == lim
         n = lim

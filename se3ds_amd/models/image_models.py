@@ -362,7 +362,7 @@ class ResNetGenerator(_Model):
     hidden, skip = self.encoder(ctx, x, mask)   # (marks its own segments)
     if sn_ev is not None:
       torch.cuda.current_stream(ctx.device).wait_event(sn_ev)
-    taps = getattr(ctx, 'taps', None)
+    taps = ctx.taps
     if taps is not None:
       taps.update(b1=skip[0], s1=skip[1], s2=skip[2], s3=skip[3], enc=hidden)
     if self.context_layer == 'convs':

@@ -46,6 +46,44 @@ def _oracle_sum(gp, dp, shard, world, double):
   return out
 
 
+def _syncbn_without_a_gradient(group, world, dev):
+  """Batch norms whose output receives no gradient (nn._norm_bwd with dy None under sync_bwd): their
+  zero contribution still joins the backward collective -- alone for a norm outside the branches,
+  and as the twin of the other branch's real sums for a whole branch without a gradient (one 8 x 32
+  tile, n = 2, 64 channels, bf16).  Without it the other replica / the twin would wait for ever, or
+  the tape would end with an 'unpaired SyncBN backward'."""
+  from se3ds_amd.hipops import nn
+  store = nn.ParamStore()
+  lone = nn.NormLayer(store, 'lone', 64)
+  bns = {t: [nn.NormLayer(store, f'b{t}_{i}', 64) for i in range(2)] for t in (1, 2)}
+  store.finalize(dev, torch.Generator().manual_seed(3))
+  ctx = nn.Ctx(dev, torch.bfloat16, training=True, record=True, group=group, world=world)
+  g = torch.Generator(device=dev).manual_seed(17 + dist.get_rank())
+  xs = {t: nn.Var(torch.randn((2, 8, 32, 64), generator=g, device=dev).to(torch.bfloat16))
+        for t in (0, 1, 2)}
+  nn.norm_act(ctx, xs[0], lone, act=nn.ACT_RELU)   # (its output is dropped: no gradient)
+  def branch(t):
+    def run():
+      h = nn.norm_act(ctx, xs[t], bns[t][0], act=nn.ACT_RELU)
+      return nn.norm_act(ctx, h, bns[t][1], act=nn.ACT_NONE)
+    return run
+  outs = ctx.run_branches({1: branch(1), 2: branch(2)})
+  assert ctx.collectives == 3, ctx.collectives   # forward: lone + 2 pairs
+  outs[1].grad = torch.randn(outs[1].data.shape, generator=g, device=dev).to(torch.bfloat16)
+  # (branch 2 gets none)
+  store.grad   # (allocates the zeroed gradient arena)
+  ctx.backward()   # (asserts that no paired SyncBN backward is left parked)
+  torch.cuda.synchronize()
+  assert ctx.collectives == 6, ctx.collectives   # backward: 2 pairs (real + zeros) + lone (zeros)
+  assert xs[1].grad is not None and bool(torch.isfinite(xs[1].grad.float()).all())
+  assert xs[0].grad is None and xs[2].grad is None
+  gv = store.grad_views
+  assert float(gv['b1_0/gamma'].abs().sum()) > 0 and float(gv['b1_1/beta'].abs().sum()) > 0
+  for name in ('lone', 'b2_0', 'b2_1'):
+    assert float(gv[name + '/gamma'].abs().sum()) == 0 and float(gv[name + '/beta'].abs().sum()) == 0
+  return ctx.collectives
+
+
 def main():
   # a hang must be visible: dump every thread's stack, then die with a non-zero status
   faulthandler.enable()
@@ -143,7 +181,9 @@ image_models.SNMultiScaleDiscriminator.n_layers = 3
   ls = [torch.zeros_like(loss) for _ in range(world)]
   dist.all_gather(ls, loss)
   assert abs(float(ls[0]) - float(ls[1])) > 0, 'both ranks report the same local loss'
+  n_coll = _syncbn_without_a_gradient(gan.strategy.group, world, dev)
   if rank == 0:
+    print(f'NO_GRAD_SYNCBN_OK collectives={n_coll}')
     ctx_probe = gan.generator.make_ctx(training=True, record=False, group=gan.strategy.group, world=world)
     print('streams=%d' % (0 if ctx_probe.streams is None else len(ctx_probe.streams)))
     print('DIST_GPU_OK', [float(x).hex() for x in got[0]])

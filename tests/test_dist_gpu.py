@@ -40,6 +40,8 @@ def test_two_replicas_share_one_gpu_over_gloo(own_comm):
   r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=300)
   assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-6000:]
   assert 'DIST_GPU_OK' in r.stdout
+  # (the worker's last case: batch norms without a gradient still join the backward collectives)
+  assert 'NO_GRAD_SYNCBN_OK collectives=6' in r.stdout
   print(r.stdout[-600:])
 
 
