@@ -3,7 +3,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <mutex>
+#include <unordered_map>
+
 #include "../../include/se3ds_hip.h"
+#include "conv_route.h"
 
 namespace se3ds {
 
@@ -19,36 +23,8 @@ inline int check_launch(const char* where) {
   return SE3DS_OK;
 }
 
-// Test hook (se3ds_debug_last_conv_route): every dispatcher of the convolution family names the
-// kernel instantiation it is about to launch -- one entry per template instantiation that differs in
-// tile shape, MFMA shape (m16 = 16x16x32, m32 = 32x32x16), dtype, mode or fused-BN flag.  Host only:
-// a thread_local ring of the calling thread's last launches, no device work.
-#define SE3DS_CONV_ROUTES(X)                                                                      \
-  X(thin_s2_dgrad) X(thin_cin_fwd) X(thin_cout_dgrad) X(thin_cout_fwd)                             \
-  X(halo256_fwd_m16) X(halo256_dgrad_m16) X(halo256_dgrad_bn_m16)                                  \
-  X(halo256_fwd_m32) X(halo256_dgrad_m32) X(halo256_dgrad_bn_m32)                                  \
-  X(halo128_fwd_m16) X(halo128_dgrad_m16) X(halo128_dgrad_bn_m16)                                  \
-  X(halo128_fwd_m32) X(halo128_dgrad_m32) X(halo128_dgrad_bn_m32)                                  \
-  X(big256_fwd_m16) X(big256_dgrad_m16) X(big256_dgrad_bn_m16)                                     \
-  X(big256_fwd_m32) X(big256_dgrad_m32) X(big256_dgrad_bn_m32)                                     \
-  X(big128_fwd_m16) X(big128_dgrad_m16) X(big128_dgrad_bn_m16)                                     \
-  X(big128_fwd_m32) X(big128_dgrad_m32) X(big128_dgrad_bn_m32)                                     \
-  X(glds_f32_fwd) X(glds_f32_dgrad)                                                                \
-  X(glds_bf16_fwd_m16) X(glds_bf16_dgrad_m16) X(glds_bf16_dgrad_bn_m16)                            \
-  X(glds_bf16_fwd_m32) X(glds_bf16_dgrad_m32) X(glds_bf16_dgrad_bn_m32)                            \
-  X(igemm_f32_fwd) X(igemm_f32_dgrad) X(igemm_bf16_fwd) X(igemm_bf16_dgrad)                        \
-  X(wgrad_taps3_m16) X(wgrad_taps3_m32) X(wgrad_taps_wrap) X(thin_cin_wgrad)                       \
-  X(wgrad_glds_f32) X(wgrad_glds_bf16) X(wgrad_f32) X(wgrad_bf16)                                  \
-  X(wgrad_reduce_vec) X(wgrad_reduce_scalar) X(wgrad_reduce_multi)                                 \
-  X(thin_cout_wgrad_t2) X(thin_cout_wgrad_t3) X(thin_cout_wgrad_t4) X(thin_cout_wgrad_t5)          \
-  X(pad_channels8) X(wgrad_taps_thin) X(wgrad_swap_fixup)                                          \
-  X(weight_prep_f32) X(weight_prep_bf16) X(weight_prep_vec) X(weight_prep_multi)
-enum ConvRoute {
-#define SE3DS_ROUTE_ENUM(name) kRoute_##name,
-  SE3DS_CONV_ROUTES(SE3DS_ROUTE_ENUM)
-#undef SE3DS_ROUTE_ENUM
-  kConvRouteCount
-};
+// The convolution family's routes (SE3DS_CONV_ROUTES, enum ConvRoute) and the choice among them:
+// conv_route.h.  SE3DS_LAUNCH names the kernel instantiation a dispatcher is about to launch.
 void note_conv_route(int route);   // defined in conv.hip
 #define SE3DS_LAUNCH(route, ...)                       \
   do {                                                 \
@@ -57,6 +33,20 @@ void note_conv_route(int route);   // defined in conv.hip
   } while (0)
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
+
+// Raises a kernel's dynamic LDS limit to `bytes`, once per kernel and size (hipFuncSetAttribute on
+// every launch is host time for nothing).  false: the runtime refused.
+inline bool ensure_dynamic_lds(const void* fn, size_t bytes) {
+  static std::mutex mu;
+  static std::unordered_map<const void*, size_t> done;
+  std::lock_guard<std::mutex> lock(mu);
+  auto it = done.find(fn);
+  if (it != done.end() && it->second >= bytes) return true;
+  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
+    return false;
+  done[fn] = bytes;
+  return true;
+}
 
 constexpr int kWave = 64;
 

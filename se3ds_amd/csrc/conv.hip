@@ -32,13 +32,10 @@ typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(4))) short s16x4_t;
 typedef __attribute__((ext_vector_type(16))) float f32x16_t;
 
-constexpr int BM = 128;     // pixels per tile
-constexpr int BN = 128;     // output channels per tile
+// (BM, BN and the other tile sizes the dispatchers' gates read: conv_route.h)
 constexpr int kThreads = 256;
 constexpr int ROWB = 64;    // bytes per LDS row (one K step)
 constexpr int TILE_BYTES = 128 * ROWB;  // one operand tile: 8 KiB
-
-enum { MODE_FWD = 0, MODE_DGRAD = 1 };
 
 template <typename T> struct TT;
 template <> struct TT<float> {
@@ -1943,7 +1940,6 @@ struct WgradParams {
   int linear_k;                       // thin Cin: tile rows are the linear (tap, ci) index
 };
 
-constexpr int WG_BL = 32;               // reduction pixels per step
 constexpr int WG_ROWB_BF16 = 320;       // 128 ch * 2 B + 64 B pad (conflict-free tr reads)
 constexpr int WG_ROWB_F32 = 528;        // 128 ch * 4 B + 16 B pad
 
@@ -3196,8 +3192,6 @@ wgrad_swap_fixup_kernel(const float* __restrict__ tmp, int k, int cin, int cout,
 // patch (10 x 34 pixels x Cout) and the transposed weights W'[ci][tap * Cout + co] sit in LDS,
 // each wave builds the im2col fragments of its two rows element by element (16-bit LDS reads,
 // a few dozen per lane) and writes through the LDS-transposed full-line epilogue.
-constexpr int kThinDRows = 8, kThinCols = 32;
-constexpr int kThinDCinMax = 256;
 __global__ void __launch_bounds__(256)
 thin_cout_dgrad_kernel(const IgemmParams p) {
   constexpr int NI = 2;   // 64 output channels per pass (32 accumulator registers per lane less than 128 channels per pass)
@@ -3326,7 +3320,7 @@ thin_cout_dgrad_kernel(const IgemmParams p) {
 // "thin-Cout forward" over a dy patch in LDS: MFMA A = the <= 4 weight rows W[(tap, ci)][co],
 // B = 16-byte patch reads.  Workgroup tile: 8 x 64 output pixels = 4 classes x 4 rows x 32
 // columns; wave w takes class row w of every class.
-constexpr int kThinSRows = 8, kThinSCols = 64, kThinSPH = 5, kThinSPW = 33;
+constexpr int kThinSPH = 5, kThinSPW = 33;
 __global__ void __launch_bounds__(256)
 thin_s2_dgrad_kernel(const IgemmParams p) {
   constexpr int C = 128, PB = C * 2 + 16;   // dy channels, bytes per patch pixel
@@ -3431,8 +3425,7 @@ thin_s2_dgrad_kernel(const IgemmParams p) {
 // MFMA operands are gathered with 16-bit LDS reads (pixels are the reduction dimension, so both
 // need 8 pixels per lane), the K/32 x 4 accumulator tiles stay in registers across all tiles of
 // the workgroup and leave as one partial slab per workgroup for wgrad_reduce_kernel.
-constexpr int kThinKMax = 256, kThinCinMax = 8;
-constexpr int kThinWRows = 8, kThinWThreads = 512, kThinWDyStride = 128 * 2 + 8;   // bytes per dy pixel
+constexpr int kThinWThreads = 512, kThinWDyStride = 128 * 2 + 8;   // bytes per dy pixel
 struct ThinCinWgradParams {
   const uint16_t* x; const uint16_t* dy; float* part;
   int N, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad_t, pad_l, wrap_w;
@@ -3615,7 +3608,6 @@ struct ThinCoutWgradParams {
   const uint16_t* x; const uint16_t* dy; float* part;
   int N, H, W, Cin, Cout, pad;
 };
-constexpr int kThinQRows = 8, kThinQSlabs = 256;   // 8 x 32 pixel tiles, one 8-wave workgroup per CU
 // (4-row tiles with two workgroups per CU measured slower: 895 vs 787 us)
 __host__ __device__ inline int thin_cw_pixel_bytes(int cin) { return cin * 2 + 32; }
 __host__ __device__ inline size_t thin_cout_wgrad_lds(int cin) {
@@ -3797,7 +3789,7 @@ thin_cout_wgrad_kernel(const ThinCoutWgradParams p) {
 // the (masked) input patch once and each of the 8 waves builds the im2col fragments of its two
 // rows with 16-bit LDS gathers through an offset table; full-line stores through the LDS
 // epilogue (two 64-channel halves per wave to keep its scratch small).  LDS is sized per layer.
-constexpr int kThinFRows = 16, kThinFThreads = 512;
+constexpr int kThinFThreads = 512;
 struct ThinCinLds {
   int kp, ws, ph, pw;
   size_t xs_off, wk_off, koff_off, bytes;
@@ -3960,7 +3952,7 @@ thin_cin_fwd_kernel(const IgemmParams p) {
 // MFMAs whose A operand has only those rows populated: 9 * Cin / 16 MFMAs per wave, patch
 // overhead 1.6x (mostly L2 hits), two workgroups per CU so that one fills while the other
 // computes.
-constexpr int kThinRows = 4, kThinPH = kThinRows + 2, kThinPW = kThinCols + 2;
+constexpr int kThinPH = kThinRows + 2, kThinPW = kThinCols + 2;
 __host__ __device__ inline int thin_pixel_bytes(int cin) { return cin * 2 + 16; }
 __host__ __device__ inline int thin_weight_bytes(int cin) { return 9 * cin * 2 + 16; }
 __host__ __device__ inline size_t thin_lds_bytes(int cin, int cout) {
@@ -4234,86 +4226,82 @@ void note_conv_route(int route) { t_route_ring[t_route_n++ % kRouteRing] = route
 using namespace se3ds;
 
 
-// SE3DS_NO_THIN=1: the thin-layer kernels (Cin <= 8 forward / weight gradient, Cout <= 4 forward /
-// data / weight gradient, the 4x4 stride-2 data gradient into <= 4 channels) are skipped and their
-// layers take the general implicit-GEMM kernels (read per call: tests/test_nets_gpu.py compares the
-// two routings on the production heads and stems).
-static bool thin_on() { return getenv("SE3DS_NO_THIN") == nullptr; }
-
-// SE3DS_BIG_TILE: unset = cost model below, 0 = never, 1 = whenever the shape allows (read per
-// call so that tests can switch it).
-static int big_tile_mode() {
-  const char* e = getenv("SE3DS_BIG_TILE");
-  return e ? atoi(e) : -1;
+// The family's five switches, read per call so that tests can flip them in-process
+// (tests/test_nets_gpu.py compares the routings on the production heads and stems).  What each
+// value means and which gate reads it: ConvSwitches and conv_route in conv_route.h.
+static ConvSwitches conv_switches() {
+  const auto num = [](const char* e, int unset) { return e ? atoi(e) : unset; };
+  ConvSwitches sw;
+  sw.thin = getenv("SE3DS_NO_THIN") == nullptr;
+  sw.big_tile = num(getenv("SE3DS_BIG_TILE"), -1);
+  sw.halo_tile = num(getenv("SE3DS_HALO_TILE"), -1);
+  // (m16 against m32, step A/B on one box, 256-channel tile only: 204.3 / 202.6 -> 200.2 / 200.0 ms)
+  sw.m16 = num(getenv("SE3DS_HALO_M16"), 1) != 0;
+  sw.fused_bn_stats = num(getenv("SE3DS_FUSED_BN_STATS"), 2);
+  return sw;
 }
 
-// Output channels per 256-pixel macro tile (256 / 128) or 0 for the 128 x 128 kernel.  Measured
-// (tools/conv_bench.py): the 256-channel macro tile runs one workgroup per CU at ~1.25x the
-// per-CU rate of two resident 128 x 128 tiles, so it wins unless its coarser grid leaves CUs
-// idle in the last round; the 128-channel variant does not beat the 128 x 128 kernel and is
-// only taken when forced (tests).
-// SE3DS_HALO_TILE: unset = heuristic, 0 = never, 1 = whenever the shape allows, 128 / 256 = force
-// that channel width.
-static int halo_tile_channels(const IgemmParams& p) {
-  const char* e = getenv("SE3DS_HALO_TILE");
-  const int mode = e ? atoi(e) : -1;
-  if (mode == 0) return 0;
-  if ((p.oC % 128) != 0) return 0;
-  if (mode == 128 || (p.oC % 256) != 0) return 128;
-  if (mode == 256) return 256;
-  // 256 channels per workgroup unless that leaves a large part of the chip without work
-  const int64_t tiles = (int64_t)p.N * ceil_div(p.oH, 8) * ceil_div(p.oW, 32);
-  const int64_t items256 = tiles * (p.oC / 256);
-  const double eff256 = (double)items256 / (double)(ceil_div(items256, (int64_t)256) * 256);
-  const int64_t items128 = items256 * 2;
-  const double eff128 = 0.85 * (double)items128 / (double)(ceil_div(items128, (int64_t)256) * 256);
-  return eff256 >= eff128 ? 256 : 128;
+// Every forward / data-gradient kernel: the route's name, its instantiation and its workgroup size,
+// bound here and nowhere else.  conv_route's id is the index.
+struct IgemmKernel {
+  ConvRoute route;
+  void (*fn)(const IgemmParams);
+  int threads;
+};
+#define SE3DS_IGEMM(name, threads, ...) {kRoute_##name, __VA_ARGS__, threads}
+static constexpr IgemmKernel kIgemmKernels[kIgemmRouteCount] = {
+    SE3DS_IGEMM(thin_s2_dgrad, 256, thin_s2_dgrad_kernel),
+    SE3DS_IGEMM(thin_cin_fwd, kThinFThreads, thin_cin_fwd_kernel),
+    SE3DS_IGEMM(thin_cout_dgrad, 256, thin_cout_dgrad_kernel),
+    SE3DS_IGEMM(thin_cout_fwd, 256, thin_cout_fwd_kernel),
+    SE3DS_IGEMM(halo256_fwd_m16, 512, igemm_halo_kernel<MODE_FWD, 256, 2, false, true>),
+    SE3DS_IGEMM(halo256_dgrad_m16, 512, igemm_halo_kernel<MODE_DGRAD, 256, 2, false, true>),
+    SE3DS_IGEMM(halo256_dgrad_bn_m16, 512, igemm_halo_kernel<MODE_DGRAD, 256, 2, true, true>),
+    SE3DS_IGEMM(halo256_fwd_m32, 512, igemm_halo_kernel<MODE_FWD, 256, 2>),
+    SE3DS_IGEMM(halo256_dgrad_m32, 512, igemm_halo_kernel<MODE_DGRAD, 256, 2>),
+    SE3DS_IGEMM(halo256_dgrad_bn_m32, 512, igemm_halo_kernel<MODE_DGRAD, 256, 2, true>),
+    SE3DS_IGEMM(halo128_fwd_m16, 512, igemm_halo_kernel<MODE_FWD, 128, 3, false, true>),
+    SE3DS_IGEMM(halo128_dgrad_m16, 512, igemm_halo_kernel<MODE_DGRAD, 128, 3, false, true>),
+    SE3DS_IGEMM(halo128_dgrad_bn_m16, 512, igemm_halo_kernel<MODE_DGRAD, 128, 3, true, true>),
+    SE3DS_IGEMM(halo128_fwd_m32, 512, igemm_halo_kernel<MODE_FWD, 128, 3>),
+    SE3DS_IGEMM(halo128_dgrad_m32, 512, igemm_halo_kernel<MODE_DGRAD, 128, 3>),
+    SE3DS_IGEMM(halo128_dgrad_bn_m32, 512, igemm_halo_kernel<MODE_DGRAD, 128, 3, true>),
+    SE3DS_IGEMM(big256_fwd_m16, 512, igemm_big_kernel<MODE_FWD, 256, false, true>),
+    SE3DS_IGEMM(big256_dgrad_m16, 512, igemm_big_kernel<MODE_DGRAD, 256, false, true>),
+    SE3DS_IGEMM(big256_dgrad_bn_m16, 512, igemm_big_kernel<MODE_DGRAD, 256, true, true>),
+    SE3DS_IGEMM(big256_fwd_m32, 512, igemm_big_kernel<MODE_FWD, 256>),
+    SE3DS_IGEMM(big256_dgrad_m32, 512, igemm_big_kernel<MODE_DGRAD, 256>),
+    SE3DS_IGEMM(big256_dgrad_bn_m32, 512, igemm_big_kernel<MODE_DGRAD, 256, true>),
+    SE3DS_IGEMM(big128_fwd_m16, 512, igemm_big_kernel<MODE_FWD, 128, false, true>),
+    SE3DS_IGEMM(big128_dgrad_m16, 512, igemm_big_kernel<MODE_DGRAD, 128, false, true>),
+    SE3DS_IGEMM(big128_dgrad_bn_m16, 512, igemm_big_kernel<MODE_DGRAD, 128, true, true>),
+    SE3DS_IGEMM(big128_fwd_m32, 512, igemm_big_kernel<MODE_FWD, 128>),
+    SE3DS_IGEMM(big128_dgrad_m32, 512, igemm_big_kernel<MODE_DGRAD, 128>),
+    SE3DS_IGEMM(big128_dgrad_bn_m32, 512, igemm_big_kernel<MODE_DGRAD, 128, true>),
+    SE3DS_IGEMM(glds_f32_fwd, kThreads, igemm_glds_kernel<float, MODE_FWD>),
+    SE3DS_IGEMM(glds_f32_dgrad, kThreads, igemm_glds_kernel<float, MODE_DGRAD>),
+    SE3DS_IGEMM(glds_bf16_fwd_m16, kThreads, igemm_glds_kernel<uint16_t, MODE_FWD, false, true>),
+    SE3DS_IGEMM(glds_bf16_dgrad_m16, kThreads, igemm_glds_kernel<uint16_t, MODE_DGRAD, false, true>),
+    SE3DS_IGEMM(glds_bf16_dgrad_bn_m16, kThreads, igemm_glds_kernel<uint16_t, MODE_DGRAD, true, true>),
+    SE3DS_IGEMM(glds_bf16_fwd_m32, kThreads, igemm_glds_kernel<uint16_t, MODE_FWD>),
+    SE3DS_IGEMM(glds_bf16_dgrad_m32, kThreads, igemm_glds_kernel<uint16_t, MODE_DGRAD>),
+    SE3DS_IGEMM(glds_bf16_dgrad_bn_m32, kThreads, igemm_glds_kernel<uint16_t, MODE_DGRAD, true>),
+    SE3DS_IGEMM(igemm_f32_fwd, kThreads, igemm_kernel<float, MODE_FWD>),
+    SE3DS_IGEMM(igemm_f32_dgrad, kThreads, igemm_kernel<float, MODE_DGRAD>),
+    SE3DS_IGEMM(igemm_bf16_fwd, kThreads, igemm_kernel<uint16_t, MODE_FWD>),
+    SE3DS_IGEMM(igemm_bf16_dgrad, kThreads, igemm_kernel<uint16_t, MODE_DGRAD>),
+};
+#undef SE3DS_IGEMM
+static constexpr bool igemm_kernels_in_route_order() {
+  for (int i = 0; i < kIgemmRouteCount; ++i)
+    if (kIgemmKernels[i].route != i || kIgemmKernels[i].fn == nullptr) return false;
+  return true;
 }
+static_assert(igemm_kernels_in_route_order(), "kIgemmKernels[i] must be the kernel of route i");
 
-// SE3DS_HALO_M16: the LDS-DMA forward / data-gradient kernels (halo, 256-pixel macro tile, 128 x 128)
-// and the tap-fused weight gradient with v_mfma_f32_16x16x32_bf16 (default; 0 = 32x32x16; read per call).  Step A/B on one box, 256-channel tile only: 204.3 / 202.6 -> 200.2 / 200.0 ms.
-static bool halo_m16() {
-  const char* e = getenv("SE3DS_HALO_M16");
-  return e ? atoi(e) != 0 : true;
-}
-
-static int big_tile_channels(const IgemmParams& p, int mode) {
-  const int g_big_tile = big_tile_mode();
-  if (g_big_tile == 0) return 0;
-  const int co = (p.oC % 256) == 0 ? 256 : ((p.oC % 128) == 0 ? 128 : 0);
-  if (!co) return 0;
-  if (g_big_tile == 1) return co;
-  int64_t m = 0;   // pixel rows over all parity classes
-  const int s = mode == MODE_FWD ? 1 : p.stride;
-  for (int py = 0; py < s; ++py)
-    for (int px = 0; px < s; ++px)
-      m += (int64_t)p.N * ((p.oH - py + s - 1) / s) * ((p.oW - px + s - 1) / s);
-  const double kCus = 256.0;
-  const double big_items = (double)ceil_div(m, (int64_t)256) * (p.oC / co);
-  const double small_items = (double)ceil_div(m, (int64_t)128) * ceil_div(p.oC, 128);
-  if (co != 256) return 0;
-  const double gain = 1.25;
-  // time in units of one 128 x 128 tile on a CU that holds two of them
-  const double t_small = std::ceil(small_items / (2 * kCus)) * 2.0;
-  const double t_big = std::ceil(big_items / kCus) * (co == 256 ? 4.0 : 2.0) / gain;
-  return t_big < t_small ? co : 0;
-}
-
-// Rows of the [rows][2][oC] column-sum array the routed FORWARD kernel emits from its epilogue
-// (one row per 64-pixel wave tile), or 0 when that kernel cannot (fp32, scalar gather, ragged
-// channel tiles).  Must follow conv_common's routing order: halo, 256-pixel macro tile, 128 x 128.
-static int64_t fwd_stats_rows(const IgemmParams& p, int dtype, int stride, int kh, int kw,
-                              bool glds, int mode = MODE_FWD) {
-  if (!glds || dtype != SE3DS_BF16) return 0;
-  // data gradient (fused batch-norm backward statistics): stride 1 only -- one parity class,
-  // the same tile geometry as a forward pass over the gradient's pixels
-  if (mode == MODE_DGRAD && stride != 1) return 0;
-  const int64_t M = (int64_t)p.N * p.oH * p.oW;
-  if (stride == 1 && kh == 3 && kw == 3 && halo_tile_channels(p))
-    return (int64_t)p.N * ceil_div(p.oH, 8) * ceil_div(p.oW, 32) * 4;
-  if (big_tile_channels(p, mode)) return ceil_div(M, (int64_t)256) * 4;
-  if ((p.oC % BN) == 0) return ceil_div(M, (int64_t)BM) * (BM / 64);
-  return 0;
+// persistent grid: one workgroup per tile up to `resident` of them on the chip
+static dim3 persistent_grid(int64_t tiles, int64_t resident) {
+  return dim3((unsigned)(tiles < resident ? tiles : resident));
 }
 
 extern "C" {
@@ -4365,8 +4353,15 @@ static int conv_common(int mode, const void* src, const void* w, void* out, int 
   p.stats = nullptr;
   p.addend = addend;
   hipStream_t s = as_stream(stream);
-  const bool glds = (p.sC % (2 * bk)) == 0 && (src_mask == nullptr || mask_binary);
-  if (stats != nullptr && !(fwd_stats_rows(p, dtype, stride, kh, kw, glds, mode) > 0))
+  ConvCall c;
+  c.mode = mode; c.dtype = dtype; c.n = n; c.h = h; c.w = wdt; c.cin = cin; c.ho = ho; c.wo = wo;
+  c.cout = cout; c.kh = kh; c.kw = kw; c.stride = stride; c.pad_t = pad_t; c.pad_l = pad_l;
+  c.wrap_w = wrap_w;
+  c.mask = src_mask == nullptr ? kMaskNone : (mask_binary ? kMaskBinary : kMaskFractional);
+  c.row_a = row_a != nullptr; c.bias = bias != nullptr; c.act = act != 0; c.stats = stats != nullptr;
+  c.addend = addend != nullptr; c.bn_x = bn_x != nullptr; c.pitched = pitched;
+  const ConvChoice ch = conv_route(c, conv_switches());
+  if (stats != nullptr && ch.stats_rows == 0)
     return SE3DS_E_UNSUPPORTED;   // callers ask se3ds_conv2d_{fwd_stats,dgrad_bnstats}_rows first
   if (stats != nullptr && mode == MODE_DGRAD &&
       (bn_x == nullptr || bn_mean == nullptr || bn_rstd == nullptr || (p.oC & 7) != 0))
@@ -4375,139 +4370,56 @@ static int conv_common(int mode, const void* src, const void* w, void* out, int 
   p.bn_x = (mode == MODE_DGRAD && stats != nullptr) ? (const uint16_t*)bn_x : nullptr;
   p.bn_mask = bn_mask; p.bn_mean = bn_mean; p.bn_rstd = bn_rstd;
   p.bn_act = bn_act; p.bn_alpha = bn_alpha;
-  if (mode == MODE_DGRAD && dtype == SE3DS_BF16 && kh == 4 && kw == 4 && stride == 2 && cin <= 4 &&
-      cout == 128 && src_mask == nullptr && row_a == nullptr && bias == nullptr && act == 0 &&
-      !wrap_w && (pad_t == 0 || pad_t == 2) && (pad_l == 0 || pad_l == 2) &&
-      thin_on()) {
-    int64_t blocks = (int64_t)p.N * ceil_div(p.oH, kThinSRows) * ceil_div(p.oW, kThinSCols);
-    if (blocks > 2 * 256) blocks = 2 * 256;   // persistent, two workgroups per CU
-    SE3DS_LAUNCH(thin_s2_dgrad, thin_s2_dgrad_kernel, dim3((unsigned)blocks), dim3(256), 0, s, p);
-    return check_launch("conv2d_dgrad(thin s2)");
-  }
-  if (mode == MODE_FWD && dtype == SE3DS_BF16 && cin <= kThinCinMax && (cout % 128) == 0 &&
-      kh * kw * cin <= kThinKMax && kh <= 7 && kw <= 7 && stats == nullptr && addend == nullptr &&
-      !pitched && thin_on()) {
-    const ThinCinLds L = thin_cin_lds(kh, kw, cin, stride);
-    static size_t lds_set = 0;
-    if (L.bytes > lds_set) {
-      if (hipFuncSetAttribute((const void*)thin_cin_fwd_kernel,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.bytes) != hipSuccess)
-        return SE3DS_E_LAUNCH;
-      lds_set = L.bytes;
-    }
-    int64_t blocks = (int64_t)p.N * ceil_div(p.oH, kThinFRows) * ceil_div(p.oW, kThinCols);
-    const int64_t resident = 256;   // persistent: one 8-wave workgroup per CU (register bound)
-    if (blocks > resident) blocks = resident;
-    SE3DS_LAUNCH(thin_cin_fwd, thin_cin_fwd_kernel, dim3((unsigned)blocks), dim3(kThinFThreads),
-                 L.bytes, s, p);
-    return check_launch("conv2d_fwd(thin cin)");
-  }
-  if (mode == MODE_DGRAD && dtype == SE3DS_BF16 && kh == 3 && kw == 3 && stride == 1 && cout <= 4 &&
-      (cin % 64) == 0 && cin <= kThinDCinMax && src_mask == nullptr && row_a == nullptr &&
-      thin_on()) {
-    int64_t blocks = (int64_t)p.N * ceil_div(p.oH, kThinDRows) * ceil_div(p.oW, kThinCols);
-    // persistent: two workgroups per CU (236 registers per lane: the third does not fit, and a grid
-    // of three per CU ran its last third at half occupancy)
-    if (blocks > 2 * 256) blocks = 2 * 256;
-    SE3DS_LAUNCH(thin_cout_dgrad, thin_cout_dgrad_kernel, dim3((unsigned)blocks), dim3(256), 0, s, p);
-    return check_launch("conv2d_dgrad(thin)");
-  }
-  if (mode == MODE_FWD && dtype == SE3DS_BF16 && kh == 3 && kw == 3 && stride == 1 && cout <= 4 &&
-      (cin % 64) == 0 && cin <= 128 && src_mask == nullptr && row_a == nullptr &&
-      stats == nullptr && addend == nullptr && thin_on()) {
-    const size_t lds = thin_lds_bytes(cin, cout);
-    static size_t lds_set = 0;
-    if (lds > lds_set) {
-      if (hipFuncSetAttribute((const void*)thin_cout_fwd_kernel,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return SE3DS_E_LAUNCH;
-      lds_set = lds;
-    }
-    int64_t blocks = (int64_t)p.N * ceil_div(p.oH, kThinRows) * ceil_div(p.oW, kThinCols);
-    if (blocks > 2 * 256) blocks = 2 * 256;   // persistent: two workgroups per CU
-    SE3DS_LAUNCH(thin_cout_fwd, thin_cout_fwd_kernel, dim3((unsigned)blocks), dim3(256), lds, s, p);
-    return check_launch("conv2d_fwd(thin)");
-  }
-  if (glds && dtype == SE3DS_BF16 && stride == 1 && kh == 3 && kw == 3) {
-    const int co = halo_tile_channels(p);
-    if (co) {
+  // the grid (and the dynamic LDS) of the chosen family; the thin grids are persistent
+  static const char* const kWhere[8][2] = {
+      {nullptr, "conv2d_dgrad(thin s2)"}, {"conv2d_fwd(thin cin)", nullptr},
+      {nullptr, "conv2d_dgrad(thin)"},    {"conv2d_fwd(thin)", nullptr},
+      {"conv2d_fwd(halo)", "conv2d_dgrad(halo)"}, {"conv2d_fwd(big)", "conv2d_dgrad(big)"},
+      {"conv2d_fwd(glds)", "conv2d_dgrad(glds)"}, {"conv2d_fwd", "conv2d_dgrad"}};
+  dim3 grid;
+  size_t lds = 0;
+  switch (ch.family) {
+    case ConvFamily::ThinS2Dgrad:   // two workgroups per CU
+      grid = persistent_grid((int64_t)p.N * ceil_div(p.oH, kThinSRows) * ceil_div(p.oW, kThinSCols), 2 * 256);
+      break;
+    case ConvFamily::ThinCinFwd:    // one 8-wave workgroup per CU (register bound)
+      lds = thin_cin_lds(kh, kw, cin, stride).bytes;
+      grid = persistent_grid((int64_t)p.N * ceil_div(p.oH, kThinFRows) * ceil_div(p.oW, kThinCols), 256);
+      break;
+    case ConvFamily::ThinCoutDgrad:
+      // two workgroups per CU (236 registers per lane: the third does not fit, and a grid of three
+      // per CU ran its last third at half occupancy)
+      grid = persistent_grid((int64_t)p.N * ceil_div(p.oH, kThinDRows) * ceil_div(p.oW, kThinCols), 2 * 256);
+      break;
+    case ConvFamily::ThinCoutFwd:   // two workgroups per CU
+      lds = thin_lds_bytes(cin, cout);
+      grid = persistent_grid((int64_t)p.N * ceil_div(p.oH, kThinRows) * ceil_div(p.oW, kThinCols), 2 * 256);
+      break;
+    case ConvFamily::Halo:          // one workgroup per CU
       p.halo_ty = ceil_div(p.oH, 8);
       p.halo_tx = ceil_div(p.oW, 32);
-      const int64_t items = (int64_t)p.N * p.halo_ty * p.halo_tx * (p.oC / co);
-      dim3 grid((unsigned)(items < 256 ? items : 256));   // persistent: one workgroup per CU
-      if (co == 256 && halo_m16()) {
-        if (mode == MODE_FWD) SE3DS_LAUNCH(halo256_fwd_m16, (igemm_halo_kernel<MODE_FWD, 256, 2, false, true>), grid, dim3(512), 0, s, p);
-        else if (p.bn_x) SE3DS_LAUNCH(halo256_dgrad_bn_m16, (igemm_halo_kernel<MODE_DGRAD, 256, 2, true, true>), grid, dim3(512), 0, s, p);
-        else SE3DS_LAUNCH(halo256_dgrad_m16, (igemm_halo_kernel<MODE_DGRAD, 256, 2, false, true>), grid, dim3(512), 0, s, p);
-      } else if (co == 256) {
-        if (mode == MODE_FWD) SE3DS_LAUNCH(halo256_fwd_m32, (igemm_halo_kernel<MODE_FWD, 256, 2>), grid, dim3(512), 0, s, p);
-        else if (p.bn_x) SE3DS_LAUNCH(halo256_dgrad_bn_m32, (igemm_halo_kernel<MODE_DGRAD, 256, 2, true>), grid, dim3(512), 0, s, p);
-        else SE3DS_LAUNCH(halo256_dgrad_m32, (igemm_halo_kernel<MODE_DGRAD, 256, 2>), grid, dim3(512), 0, s, p);
-      } else {
-        if (halo_m16()) {
-          if (mode == MODE_FWD) SE3DS_LAUNCH(halo128_fwd_m16, (igemm_halo_kernel<MODE_FWD, 128, 3, false, true>), grid, dim3(512), 0, s, p);
-          else if (p.bn_x) SE3DS_LAUNCH(halo128_dgrad_bn_m16, (igemm_halo_kernel<MODE_DGRAD, 128, 3, true, true>), grid, dim3(512), 0, s, p);
-          else SE3DS_LAUNCH(halo128_dgrad_m16, (igemm_halo_kernel<MODE_DGRAD, 128, 3, false, true>), grid, dim3(512), 0, s, p);
-        } else if (mode == MODE_FWD) SE3DS_LAUNCH(halo128_fwd_m32, (igemm_halo_kernel<MODE_FWD, 128, 3>), grid, dim3(512), 0, s, p);
-        else if (p.bn_x) SE3DS_LAUNCH(halo128_dgrad_bn_m32, (igemm_halo_kernel<MODE_DGRAD, 128, 3, true>), grid, dim3(512), 0, s, p);
-        else SE3DS_LAUNCH(halo128_dgrad_m32, (igemm_halo_kernel<MODE_DGRAD, 128, 3>), grid, dim3(512), 0, s, p);
-      }
-      return check_launch(mode == MODE_FWD ? "conv2d_fwd(halo)" : "conv2d_dgrad(halo)");
-    }
-  }
-  if (glds && dtype == SE3DS_BF16) {
-    const int co = big_tile_channels(p, mode);
-    if (co) {
+      grid = persistent_grid((int64_t)p.N * p.halo_ty * p.halo_tx * (p.oC / ch.channels), 256);
+      break;
+    case ConvFamily::Big: {
       const int tiles = fill_classes(p, mode, 256);
       if (tiles <= 0) return SE3DS_OK;
-      dim3 grid((unsigned)tiles, (unsigned)(p.oC / co));
-      if (co == 256 && halo_m16()) {
-        if (mode == MODE_FWD) SE3DS_LAUNCH(big256_fwd_m16, (igemm_big_kernel<MODE_FWD, 256, false, true>), grid, dim3(512), 0, s, p);
-        else if (p.bn_x) SE3DS_LAUNCH(big256_dgrad_bn_m16, (igemm_big_kernel<MODE_DGRAD, 256, true, true>), grid, dim3(512), 0, s, p);
-        else SE3DS_LAUNCH(big256_dgrad_m16, (igemm_big_kernel<MODE_DGRAD, 256, false, true>), grid, dim3(512), 0, s, p);
-      } else if (co == 256) {
-        if (mode == MODE_FWD) SE3DS_LAUNCH(big256_fwd_m32, (igemm_big_kernel<MODE_FWD, 256>), grid, dim3(512), 0, s, p);
-        else if (p.bn_x) SE3DS_LAUNCH(big256_dgrad_bn_m32, (igemm_big_kernel<MODE_DGRAD, 256, true>), grid, dim3(512), 0, s, p);
-        else SE3DS_LAUNCH(big256_dgrad_m32, (igemm_big_kernel<MODE_DGRAD, 256>), grid, dim3(512), 0, s, p);
-      } else if (halo_m16()) {
-        if (mode == MODE_FWD) SE3DS_LAUNCH(big128_fwd_m16, (igemm_big_kernel<MODE_FWD, 128, false, true>), grid, dim3(512), 0, s, p);
-        else if (p.bn_x) SE3DS_LAUNCH(big128_dgrad_bn_m16, (igemm_big_kernel<MODE_DGRAD, 128, true, true>), grid, dim3(512), 0, s, p);
-        else SE3DS_LAUNCH(big128_dgrad_m16, (igemm_big_kernel<MODE_DGRAD, 128, false, true>), grid, dim3(512), 0, s, p);
-      } else {
-        if (mode == MODE_FWD) SE3DS_LAUNCH(big128_fwd_m32, (igemm_big_kernel<MODE_FWD, 128>), grid, dim3(512), 0, s, p);
-        else if (p.bn_x) SE3DS_LAUNCH(big128_dgrad_bn_m32, (igemm_big_kernel<MODE_DGRAD, 128, true>), grid, dim3(512), 0, s, p);
-        else SE3DS_LAUNCH(big128_dgrad_m32, (igemm_big_kernel<MODE_DGRAD, 128>), grid, dim3(512), 0, s, p);
-      }
-      return check_launch(mode == MODE_FWD ? "conv2d_fwd(big)" : "conv2d_dgrad(big)");
+      grid = dim3((unsigned)tiles, (unsigned)(p.oC / ch.channels));
+      break;
+    }
+    case ConvFamily::Glds:
+    case ConvFamily::Gather: {
+      const int tiles = fill_classes(p, mode);
+      if (tiles <= 0) return SE3DS_OK;
+      grid = dim3((unsigned)tiles, (unsigned)ceil_div(p.oC, BN));
+      break;
     }
   }
-  int tiles = fill_classes(p, mode);
-  if (tiles <= 0) return SE3DS_OK;
-  dim3 grid((unsigned)tiles, (unsigned)ceil_div(p.oC, BN));
-  if (glds) {
-    if (dtype == SE3DS_F32) {
-      if (mode == MODE_FWD) SE3DS_LAUNCH(glds_f32_fwd, (igemm_glds_kernel<float, MODE_FWD>), grid, dim3(kThreads), 0, s, p);
-      else SE3DS_LAUNCH(glds_f32_dgrad, (igemm_glds_kernel<float, MODE_DGRAD>), grid, dim3(kThreads), 0, s, p);
-    } else {
-      // (the 16x16x32 epilogue has no ragged channel tiles)
-      if ((p.oC % BN) == 0 && halo_m16()) {
-        if (mode == MODE_FWD) SE3DS_LAUNCH(glds_bf16_fwd_m16, (igemm_glds_kernel<uint16_t, MODE_FWD, false, true>), grid, dim3(kThreads), 0, s, p);
-        else if (p.bn_x) SE3DS_LAUNCH(glds_bf16_dgrad_bn_m16, (igemm_glds_kernel<uint16_t, MODE_DGRAD, true, true>), grid, dim3(kThreads), 0, s, p);
-        else SE3DS_LAUNCH(glds_bf16_dgrad_m16, (igemm_glds_kernel<uint16_t, MODE_DGRAD, false, true>), grid, dim3(kThreads), 0, s, p);
-      } else if (mode == MODE_FWD) SE3DS_LAUNCH(glds_bf16_fwd_m32, (igemm_glds_kernel<uint16_t, MODE_FWD>), grid, dim3(kThreads), 0, s, p);
-      else if (p.bn_x) SE3DS_LAUNCH(glds_bf16_dgrad_bn_m32, (igemm_glds_kernel<uint16_t, MODE_DGRAD, true>), grid, dim3(kThreads), 0, s, p);
-      else SE3DS_LAUNCH(glds_bf16_dgrad_m32, (igemm_glds_kernel<uint16_t, MODE_DGRAD>), grid, dim3(kThreads), 0, s, p);
-    }
-    return check_launch(mode == MODE_FWD ? "conv2d_fwd(glds)" : "conv2d_dgrad(glds)");
-  }
-  if (dtype == SE3DS_F32) {
-    if (mode == MODE_FWD) SE3DS_LAUNCH(igemm_f32_fwd, (igemm_kernel<float, MODE_FWD>), grid, dim3(kThreads), 0, s, p);
-    else SE3DS_LAUNCH(igemm_f32_dgrad, (igemm_kernel<float, MODE_DGRAD>), grid, dim3(kThreads), 0, s, p);
-  } else {
-    if (mode == MODE_FWD) SE3DS_LAUNCH(igemm_bf16_fwd, (igemm_kernel<uint16_t, MODE_FWD>), grid, dim3(kThreads), 0, s, p);
-    else SE3DS_LAUNCH(igemm_bf16_dgrad, (igemm_kernel<uint16_t, MODE_DGRAD>), grid, dim3(kThreads), 0, s, p);
-  }
-  return check_launch(mode == MODE_FWD ? "conv2d_fwd" : "conv2d_dgrad");
+  const IgemmKernel& k = kIgemmKernels[ch.route];
+  if (lds && !ensure_dynamic_lds((const void*)k.fn, lds)) return SE3DS_E_LAUNCH;
+  note_conv_route(ch.route);
+  void* args[] = {&p};
+  (void)hipLaunchKernel((const void*)k.fn, grid, dim3((unsigned)k.threads), args, lds, s);   // (status: check_launch)
+  return check_launch(kWhere[(int)ch.family][mode == MODE_FWD ? 0 : 1]);
 }
 
 int se3ds_conv2d_fwd(const void* x, const void* wt, void* y, int dtype, int n, int h, int w,
@@ -4522,18 +4434,8 @@ int se3ds_conv2d_fwd(const void* x, const void* wt, void* y, int dtype, int n, i
 
 int64_t se3ds_conv2d_fwd_stats_rows(int dtype, int n, int cin, int ho, int wo, int cout, int kh,
                                     int kw, int stride, int has_in_mask, int in_mask_binary) {
-  if (dtype != SE3DS_BF16 || stride < 1 || stride > 2 || (cin % 64) != 0 ||
-      (has_in_mask && !in_mask_binary))
-    return 0;
-  // SE3DS_FUSED_BN_STATS: 0 = never, 1 = only the halo-resident 3x3 kernel, default = every
-  // LDS-DMA kernel
-  const char* e = getenv("SE3DS_FUSED_BN_STATS");
-  const int lvl = e ? atoi(e) : 2;
-  if (lvl == 0) return 0;
-  IgemmParams p;
-  p.N = n; p.oH = ho; p.oW = wo; p.oC = cout; p.stride = stride;
-  if (lvl == 1 && !(stride == 1 && kh == 3 && kw == 3 && halo_tile_channels(p))) return 0;
-  return fwd_stats_rows(p, dtype, stride, kh, kw, true);
+  return conv_fwd_stats_rows(dtype, n, cin, ho, wo, cout, kh, kw, stride, has_in_mask != 0,
+                             in_mask_binary != 0, conv_switches());
 }
 
 int se3ds_conv_transpose2x2_fwd(const void* x, const void* wn, void* y, int dtype, int n, int hi, int wi,
@@ -4593,11 +4495,8 @@ int se3ds_conv2d_dgrad_acc(const void* dy, const void* wn, void* dx, int dtype, 
 // rows == 0: this shape / routing cannot (strided, fp32, thin or ragged channel tiles).
 int64_t se3ds_conv2d_dgrad_bnstats_rows(int dtype, int n, int h, int w, int cin, int cout, int kh,
                                         int kw, int stride, int has_row_scale) {
-  if (dtype != SE3DS_BF16 || stride != 1 || (cout % 64) != 0 || (cin % 8) != 0 || has_row_scale)
-    return 0;
-  IgemmParams p;
-  p.N = n; p.oH = h; p.oW = w; p.oC = cin; p.stride = stride;
-  return fwd_stats_rows(p, dtype, stride, kh, kw, true, MODE_DGRAD);
+  return conv_dgrad_bnstats_rows(dtype, n, h, w, cin, cout, kh, kw, stride, has_row_scale != 0,
+                                 conv_switches());
 }
 
 int se3ds_conv2d_dgrad_bnstats(const void* dy, const void* wn, void* dx, int dtype, int n, int h,
@@ -4612,76 +4511,11 @@ int se3ds_conv2d_dgrad_bnstats(const void* dy, const void* wn, void* dx, int dty
                      stream, stats, addend, bn_x, bn_mask, bn_mean, bn_rstd, bn_act, bn_alpha);
 }
 
-static int wgrad_splits(int64_t L, int64_t tiles, int64_t nel) {
-  // Work items = tiles x splits, equal cost; ~512 run concurrently (2 per CU).  Cost model
-  // (microseconds): rounds of items x steps per item x time per 64-pixel step, plus the write +
-  // read of the fp32 partial slabs by the deterministic reduce.  Pick the cheapest split count.
-  const double kStepUs = 2.15, kBytesPerUs = 3.0e6, kSlots = 512.0;
-  int best = 1;
-  double best_cost = 1e30;
-  for (int s = 1; s <= 256; ++s) {
-    int64_t per = (L + s - 1) / s;
-    if (s > 1 && per < 256) break;
-    double steps = (double)((per + 63) / 64);
-    double rounds = (double)((tiles * s + (int64_t)kSlots - 1) / (int64_t)kSlots);
-    double cost = rounds * steps * kStepUs + (s > 1 ? 5.0 : 0.0) +
-                  (double)s * (double)nel * 8.0 / kBytesPerUs * (s > 1 ? 1.0 : 0.5);
-    if (cost < best_cost) { best_cost = cost; best = s; }
-  }
-  return best;
-}
-
-// CUs a weight-gradient launch may count on.  (With the two decoders on two streams a 128-item
-// launch of one branch shares the chip with the other branch's; counting on 128 was measured
-// 221.1 / 221.4 ms per step against 222.7 / 221.5 with 256 on one box in round 3 -- the launches of
-// the two branches do not pair up reliably: all 256.)
-static constexpr int wgrad_slots() { return 256; }
-
-// tap-fused 3x3 kernel: steps of 64 pixels, work items = (Cin/64) x (Cout/128) x splits on 256
-// single-workgroup CUs.  Returns the split count (0: shape not eligible).
-static int wgrad_taps_splits(int n, int ho, int wo, int cin, int cout, int kh, int kw, int* steps) {
-  if (kh != 3 || kw != 3 || (cin % 64) != 0 || (cout % 128) != 0) return 0;
-  const int64_t total = (int64_t)n * ceil_div(ho, 2) * ceil_div(wo, 32);
-  if (total > (1 << 30)) return 0;
-  *steps = (int)total;
-  const int64_t tiles = (int64_t)(cin / 64) * (cout / 128);
-  // rounds of 256 items x steps per item (~1.3 us each) + partial-slab traffic of the reduce
-  const double kStepUs = 1.3, kBytesPerUs = 3.0e6;
-  const int64_t nel = (int64_t)9 * cin * cout;
-  int best = 1;
-  double best_cost = 1e30;
-  for (int s = 1; s <= 512 && s <= total; ++s) {
-    const double per = (double)ceil_div(total, (int64_t)s);
-    if (s > 1 && per < 8) break;
-    const double rounds = (double)ceil_div(tiles * s, (int64_t)wgrad_slots());
-    const double cost = rounds * (per * kStepUs + 4.0) +
-                        (double)s * (double)nel * 8.0 / kBytesPerUs * (s > 1 ? 1.0 : 0.5);
-    if (cost < best_cost) { best_cost = cost; best = s; }
-  }
-  return best;
-}
-
-static bool thin_cin_wgrad_ok(int cin, int cout, int kh, int kw) {
-  return cin <= kThinCinMax && cout == 128 && kh * kw * cin <= kThinKMax && kh <= 7 && kw <= 7 &&
-         thin_on();
-}
-
+// Weight gradients: which kernel, how many splits and how large a workspace are wgrad_route,
+// wgrad_swapped_route and the two *_workspace_bytes of conv_route.h; here only parameters and launches.
 size_t se3ds_conv2d_wgrad_workspace_bytes(int n, int ho, int wo, int cin, int cout, int kh,
                                           int kw) {
-  int tsteps = 0;
-  const int tsplits = wgrad_taps_splits(n, ho, wo, cin, cout, kh, kw, &tsteps);
-  const size_t taps_bytes = sizeof(float) * (size_t)tsplits * (size_t)kh * kw * cin * cout + 16;
-  int64_t L = (int64_t)n * ho * wo;
-  int64_t row_tiles = cin <= 16 ? ceil_div((int64_t)kh * kw * cin, 128)
-                                : (int64_t)kh * kw * ceil_div(cin, 128);
-  int64_t tiles = row_tiles * ceil_div(cout, 128);
-  int splits = wgrad_splits(L, tiles, (int64_t)kh * kw * cin * cout);
-  size_t bytes = sizeof(float) * (size_t)splits * (size_t)kh * kw * cin * cout + 16;
-  if (thin_cin_wgrad_ok(cin, cout, kh, kw)) {   // one partial slab per persistent workgroup
-    const size_t thin = sizeof(float) * (size_t)256 * (size_t)kh * kw * cin * cout + 16;
-    bytes = bytes > thin ? bytes : thin;
-  }
-  return bytes > taps_bytes ? bytes : taps_bytes;
+  return wgrad_workspace_bytes(n, ho, wo, cin, cout, kh, kw, conv_switches());
 }
 
 int se3ds_conv2d_wgrad(const void* x, const void* dy, float* dw, int dtype, int n, int h, int w,
@@ -4693,85 +4527,66 @@ int se3ds_conv2d_wgrad(const void* x, const void* dy, float* dw, int dtype, int 
       kw <= 0 || stride <= 0)
     return SE3DS_E_BADSHAPE;
   if (dtype != SE3DS_F32 && dtype != SE3DS_BF16) return SE3DS_E_BADDTYPE;
-  if (workspace_bytes < se3ds_conv2d_wgrad_workspace_bytes(n, ho, wo, cin, cout, kh, kw))
+  const ConvSwitches sw = conv_switches();
+  if (workspace_bytes < wgrad_workspace_bytes(n, ho, wo, cin, cout, kh, kw, sw))
     return SE3DS_E_WORKSPACE;
   hipStream_t s = as_stream(stream);
-  if (dtype == SE3DS_BF16 && stride == 1 && row_scale == nullptr &&
-      (in_mask == nullptr || in_mask_binary)) {
-    int tsteps = 0;
-    const int tsplits = wgrad_taps_splits(n, ho, wo, cin, cout, kh, kw, &tsteps);
-    if (tsplits > 0) {
+  const ConvMask mask = in_mask == nullptr ? kMaskNone : (in_mask_binary ? kMaskBinary : kMaskFractional);
+  const WgradChoice c = wgrad_route(dtype, n, ho, wo, cin, cout, kh, kw, stride, wrap_w, mask,
+                                    row_scale != nullptr, sw);
+  const char* where = "conv2d_wgrad";
+  switch (c.route) {
+    case kRoute_wgrad_taps3_m16:
+    case kRoute_wgrad_taps3_m32:
+    case kRoute_wgrad_taps_wrap: {
       WgradTapsParams q;
       q.x = (const uint16_t*)x; q.H = h; q.W = w; q.Cin = cin;
       q.dy = (const uint16_t*)dy; q.Ho = ho; q.Wo = wo; q.Cout = cout;
       q.N = n; q.pad_t = pad_t; q.pad_l = pad_l; q.wrap_w = wrap_w; q.src_mask = in_mask;
       q.dw = (float*)workspace;
       q.steps_y = ceil_div(ho, 2); q.steps_x = ceil_div(wo, 32);
-      q.total_steps = tsteps;
-      q.steps_per_split = ceil_div(tsteps, tsplits);
+      q.total_steps = c.steps;
+      q.steps_per_split = c.steps_per_split;
       q.dy_cstride = cout; q.co_valid = cout;
-      dim3 tgrid((unsigned)(cin / 64), (unsigned)(cout / 128), (unsigned)tsplits);
-      if (!wrap_w)
-        if (halo_m16()) SE3DS_LAUNCH(wgrad_taps3_m16, wgrad_taps3_kernel<true>, tgrid, dim3(512), 0, s, q);
-        else SE3DS_LAUNCH(wgrad_taps3_m32, wgrad_taps3_kernel<false>, tgrid, dim3(512), 0, s, q);
-      else
-        SE3DS_LAUNCH(wgrad_taps_wrap, wgrad_taps_kernel, tgrid, dim3(512), 0, s, q);
-      const int64_t tnel = (int64_t)9 * cin * cout;
-      launch_wgrad_reduce((const float*)workspace, tsplits, tnel, accumulate, out_scale, dw, s);
-      return check_launch("conv2d_wgrad(taps)");
+      dim3 tgrid((unsigned)(cin / 64), (unsigned)(cout / 128), (unsigned)c.splits);
+      if (c.route == kRoute_wgrad_taps3_m16) SE3DS_LAUNCH(wgrad_taps3_m16, wgrad_taps3_kernel<true>, tgrid, dim3(512), 0, s, q);
+      else if (c.route == kRoute_wgrad_taps3_m32) SE3DS_LAUNCH(wgrad_taps3_m32, wgrad_taps3_kernel<false>, tgrid, dim3(512), 0, s, q);
+      else SE3DS_LAUNCH(wgrad_taps_wrap, wgrad_taps_kernel, tgrid, dim3(512), 0, s, q);
+      where = "conv2d_wgrad(taps)";
+      break;
+    }
+    case kRoute_thin_cin_wgrad: {
+      ThinCinWgradParams q;
+      q.x = (const uint16_t*)x; q.dy = (const uint16_t*)dy; q.part = (float*)workspace;
+      q.N = n; q.H = h; q.W = w; q.Cin = cin; q.Ho = ho; q.Wo = wo; q.Cout = cout; q.kh = kh;
+      q.kw = kw; q.stride = stride; q.pad_t = pad_t; q.pad_l = pad_l; q.wrap_w = wrap_w;
+      q.src_mask = in_mask; q.row_scale = row_scale;
+      const size_t lds = thin_cin_wgrad_lds(kh, kw, cin, stride);
+      if (!ensure_dynamic_lds((const void*)thin_cin_wgrad_kernel, lds)) return SE3DS_E_LAUNCH;
+      SE3DS_LAUNCH(thin_cin_wgrad, thin_cin_wgrad_kernel, dim3((unsigned)c.splits), dim3(kThinWThreads), lds, s, q);
+      where = "conv2d_wgrad(thin cin)";
+      break;
+    }
+    default: {
+      WgradParams p;
+      p.x = x; p.H = h; p.W = w; p.Cin = cin; p.dy = dy; p.Ho = ho; p.Wo = wo; p.Cout = cout;
+      p.N = n; p.kh = kh; p.kw = kw; p.stride = stride; p.pad_t = pad_t; p.pad_l = pad_l;
+      p.wrap_w = wrap_w; p.src_mask = in_mask; p.mask_binary = in_mask_binary; p.row_scale = row_scale;
+      p.dw = (float*)workspace;
+      p.ci_tiles = (int)ceil_div(cin, 128);
+      p.linear_k = c.linear_k;
+      p.splits = c.splits;
+      p.l_per_split = c.l_per_split;
+      dim3 grid((unsigned)c.row_tiles, (unsigned)ceil_div(cout, 128), (unsigned)c.splits);
+      if (c.route == kRoute_wgrad_glds_f32) SE3DS_LAUNCH(wgrad_glds_f32, wgrad_glds_kernel<float>, grid, dim3(kThreads), 0, s, p);
+      else if (c.route == kRoute_wgrad_glds_bf16) SE3DS_LAUNCH(wgrad_glds_bf16, wgrad_glds_kernel<uint16_t>, grid, dim3(kThreads), 0, s, p);
+      else if (c.route == kRoute_wgrad_f32) SE3DS_LAUNCH(wgrad_f32, wgrad_kernel<float>, grid, dim3(kThreads), 0, s, p);
+      else SE3DS_LAUNCH(wgrad_bf16, wgrad_kernel<uint16_t>, grid, dim3(kThreads), 0, s, p);
     }
   }
-  if (dtype == SE3DS_BF16 && stride <= 2 && thin_cin_wgrad_ok(cin, cout, kh, kw)) {
-    ThinCinWgradParams q;
-    q.x = (const uint16_t*)x; q.dy = (const uint16_t*)dy; q.part = (float*)workspace;
-    q.N = n; q.H = h; q.W = w; q.Cin = cin; q.Ho = ho; q.Wo = wo; q.Cout = cout; q.kh = kh;
-    q.kw = kw; q.stride = stride; q.pad_t = pad_t; q.pad_l = pad_l; q.wrap_w = wrap_w;
-    q.src_mask = in_mask; q.row_scale = row_scale;
-    const size_t lds = thin_cin_wgrad_lds(kh, kw, cin, stride);
-    static size_t lds_set = 0;
-    if (lds > lds_set) {
-      if (hipFuncSetAttribute((const void*)thin_cin_wgrad_kernel,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return SE3DS_E_LAUNCH;
-      lds_set = lds;
-    }
-    int64_t blocks = (int64_t)n * ceil_div(ho, kThinWRows) * ceil_div(wo, kThinCols);
-    if (blocks > 256) blocks = 256;
-    SE3DS_LAUNCH(thin_cin_wgrad, thin_cin_wgrad_kernel, dim3((unsigned)blocks), dim3(kThinWThreads), lds, s, q);
-    const int64_t tnel = (int64_t)kh * kw * cin * cout;
-    launch_wgrad_reduce((const float*)workspace, (int)blocks, tnel, accumulate, out_scale, dw, s);
-    return check_launch("conv2d_wgrad(thin cin)");
-  }
-  WgradParams p;
-  p.x = x; p.H = h; p.W = w; p.Cin = cin; p.dy = dy; p.Ho = ho; p.Wo = wo; p.Cout = cout;
-  p.N = n; p.kh = kh; p.kw = kw; p.stride = stride; p.pad_t = pad_t; p.pad_l = pad_l;
-  p.wrap_w = wrap_w; p.src_mask = in_mask; p.mask_binary = in_mask_binary; p.row_scale = row_scale;
-  p.dw = (float*)workspace;
-  p.ci_tiles = (int)ceil_div(cin, 128);
-  p.linear_k = cin <= 16 ? 1 : 0;
-  const int64_t L = (int64_t)n * ho * wo;
-  const int64_t row_tiles = p.linear_k ? ceil_div((int64_t)kh * kw * cin, 128)
-                                       : (int64_t)kh * kw * p.ci_tiles;
-  const int64_t tiles = row_tiles * ceil_div(cout, 128);
-  p.splits = wgrad_splits(L, tiles, (int64_t)kh * kw * cin * cout);
-  p.l_per_split = ceil_div(ceil_div(L, p.splits), WG_BL) * WG_BL;
-  dim3 grid((unsigned)row_tiles, (unsigned)ceil_div(cout, 128), (unsigned)p.splits);
-  const int epc = dtype == SE3DS_F32 ? 4 : 8;
-  const bool glds = !p.linear_k && (in_mask == nullptr || in_mask_binary) &&
-                    row_scale == nullptr &&
-                    (cin % epc) == 0 && (cout % epc) == 0;
-  if (glds) {
-    p.l_per_split = ceil_div(ceil_div(L, p.splits), 64) * 64;
-    if (dtype == SE3DS_F32) SE3DS_LAUNCH(wgrad_glds_f32, wgrad_glds_kernel<float>, grid, dim3(kThreads), 0, s, p);
-    else SE3DS_LAUNCH(wgrad_glds_bf16, wgrad_glds_kernel<uint16_t>, grid, dim3(kThreads), 0, s, p);
-  } else if (dtype == SE3DS_F32) {
-    SE3DS_LAUNCH(wgrad_f32, wgrad_kernel<float>, grid, dim3(kThreads), 0, s, p);
-  } else {
-    SE3DS_LAUNCH(wgrad_bf16, wgrad_kernel<uint16_t>, grid, dim3(kThreads), 0, s, p);
-  }
-  const int64_t nel = (int64_t)kh * kw * cin * cout;
-  launch_wgrad_reduce((const float*)workspace, p.splits, nel, accumulate, out_scale, dw, s);
-  return check_launch("conv2d_wgrad");
+  launch_wgrad_reduce((const float*)workspace, c.splits, (int64_t)kh * kw * cin * cout, accumulate,
+                      out_scale, dw, s);
+  return check_launch(where);
 }
 
 int se3ds_conv2d_wgrad_partial(const void* x, const void* dy, float* dw, int dtype, int n, int h,
@@ -4808,109 +4623,67 @@ uint32_t se3ds_fastdiv_host(uint32_t n, uint32_t d) {
   return (t + ((n - t) >> f.s1)) >> f.s2;
 }
 
-// thin-Cout layers through the tap-fused kernel (padded dy copy): split count, 0 = not eligible
-static int wgrad_taps_thin_splits(int n, int h, int w, int cin, int cout, int k, int* steps) {
-  if (k != 3 || cout > 8 || (cin % 64) != 0) return 0;
-  const int64_t total = (int64_t)n * ceil_div(h, 2) * ceil_div(w, 32);
-  if (total > (1 << 30)) return 0;
-  *steps = (int)total;
-  const int64_t tiles = cin / 64;
-  int64_t sp = ceil_div((int64_t)256, tiles);   // one round of the 256 CUs
-  if (sp > total / 8) sp = total / 8;
-  if (sp < 1) sp = 1;
-  return (int)sp;
-}
-
 size_t se3ds_conv2d_wgrad_swapped_workspace_bytes(int n, int h, int w, int cin, int cout, int k) {
-  const size_t a = se3ds_conv2d_wgrad_workspace_bytes(n, h, w, cout, cin, k, k) +
-                   sizeof(float) * (size_t)k * k * cin * cout + 64;
-  int steps = 0;
-  const int sp = wgrad_taps_thin_splits(n, h, w, cin, cout, k, &steps);
-  const size_t b = sp ? (size_t)n * h * w * 16 + 256 + sizeof(float) * (size_t)sp * 9 * cin * cout + 64
-                      : 0;
-  // thin_cout_wgrad_kernel: one partial slab per persistent workgroup
-  const size_t c = (k == 3 && cout <= 4) ? sizeof(float) * (size_t)kThinQSlabs * 9 * cin * cout + 64 : 0;
-  const size_t ab = a > b ? a : b;
-  return ab > c ? ab : c;
+  return wgrad_swapped_workspace_bytes(n, h, w, cin, cout, k, conv_switches());
 }
 
 int se3ds_conv2d_wgrad_swapped(const void* x, const void* dy, float* dw, int dtype, int n, int h,
                                int w, int cin, int cout, int k, int pad, int accumulate,
                                void* workspace, size_t workspace_bytes, void* stream) {
-  if (workspace_bytes < se3ds_conv2d_wgrad_swapped_workspace_bytes(n, h, w, cin, cout, k))
+  const ConvSwitches sw = conv_switches();
+  if (workspace_bytes < wgrad_swapped_workspace_bytes(n, h, w, cin, cout, k, sw))
     return SE3DS_E_WORKSPACE;
-  if (dtype == SE3DS_BF16 && k == 3 && cout <= 4 && (cin % 32) == 0 && cin <= 128 &&
-      workspace_bytes >= sizeof(float) * (size_t)kThinQSlabs * 9 * cin * cout &&
-      thin_on()) {
-    hipStream_t s = as_stream(stream);
-    ThinCoutWgradParams q;
-    q.x = (const uint16_t*)x; q.dy = (const uint16_t*)dy; q.part = (float*)workspace;
-    q.N = n; q.H = h; q.W = w; q.Cin = cin; q.Cout = cout; q.pad = pad;
-    const size_t lds = thin_cout_wgrad_lds(cin);
-    int64_t blocks = (int64_t)n * ceil_div(h, kThinQRows) * ceil_div(w, kThinCols);
-    if (blocks > kThinQSlabs) blocks = kThinQSlabs;
-    // column tiles per wave: 9 * Cin / 32 tiles dealt to 8 waves
-    const int tiles_per_wave = ceil_div(9 * (cin / 32), 8);
-#define SE3DS_THIN_CW(M)                                                                          \
-  do {                                                                                            \
-    static size_t lds_set = 0;                                                                    \
-    if (lds > lds_set) {                                                                          \
-      if (hipFuncSetAttribute((const void*)thin_cout_wgrad_kernel<M>,                             \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) \
-        return SE3DS_E_LAUNCH;                                                                    \
-      lds_set = lds;                                                                              \
-    }                                                                                             \
-    SE3DS_LAUNCH(thin_cout_wgrad_t##M, thin_cout_wgrad_kernel<M>, dim3((unsigned)blocks),         \
-                 dim3(kThinWThreads), lds, s, q);                                                 \
-  } while (0)
-    switch (tiles_per_wave) {
-      case 2: SE3DS_THIN_CW(2); break;
-      case 3: SE3DS_THIN_CW(3); break;
-      case 4: SE3DS_THIN_CW(4); break;
-      default: SE3DS_THIN_CW(5); break;
-    }
+  hipStream_t s = as_stream(stream);
+  const WgradChoice c = wgrad_swapped_route(dtype, n, h, w, cin, cout, k, sw);
+  const int64_t nel = (int64_t)k * k * cin * cout;
+  if (c.route == kRoute_wgrad_swap_fixup) {
+    // tmp[(ky',kx'),co,ci] = wgrad of the conv with input dy (cout channels), output-grad x
+    float* tmp = (float*)workspace;
+    int rc = se3ds_conv2d_wgrad(dy, x, tmp, dtype, n, h, w, cout, h, w, cin, k, k, 1, k - 1 - pad,
+                                k - 1 - pad, 0, nullptr, 0, nullptr, nullptr, 0,
+                                (char*)workspace + c.lead_bytes, workspace_bytes - c.lead_bytes, stream);
+    if (rc != SE3DS_OK) return rc;
+    SE3DS_LAUNCH(wgrad_swap_fixup, wgrad_swap_fixup_kernel, dim3(grid_for(nel, 256)), dim3(256), 0, s,
+                 tmp, k, cin, cout, accumulate, dw);
+    return check_launch("conv2d_wgrad_swapped");
+  }
+  float* part = (float*)((char*)workspace + c.lead_bytes);
+  if (c.route == kRoute_wgrad_taps_thin) {
+    const int64_t px = (int64_t)n * h * w;
+    uint16_t* dyp = (uint16_t*)workspace;
+    SE3DS_LAUNCH(pad_channels8, pad_channels8_kernel, dim3(grid_for(px, 256)), dim3(256), 0, s,
+                 (const uint16_t*)dy, cout, px, dyp);
+    WgradTapsParams q;
+    q.x = (const uint16_t*)x; q.H = h; q.W = w; q.Cin = cin;
+    q.dy = dyp; q.Ho = h; q.Wo = w; q.Cout = cout;
+    q.N = n; q.pad_t = pad; q.pad_l = pad; q.wrap_w = 0; q.src_mask = nullptr;
+    q.dw = part;
+    q.steps_y = ceil_div(h, 2); q.steps_x = ceil_div(w, 32);
+    q.total_steps = c.steps;
+    q.steps_per_split = c.steps_per_split;
+    q.dy_cstride = 8; q.co_valid = cout;
+    dim3 tgrid((unsigned)(cin / 64), 1, (unsigned)c.splits);
+    SE3DS_LAUNCH(wgrad_taps_thin, wgrad_taps_kernel, tgrid, dim3(512), 0, s, q);
+    launch_wgrad_reduce(part, c.splits, nel, accumulate, nullptr, dw, s);
+    return check_launch("conv2d_wgrad(taps, thin)");
+  }
+  ThinCoutWgradParams q;
+  q.x = (const uint16_t*)x; q.dy = (const uint16_t*)dy; q.part = part;
+  q.N = n; q.H = h; q.W = w; q.Cin = cin; q.Cout = cout; q.pad = pad;
+  const size_t lds = thin_cout_wgrad_lds(cin);
+#define SE3DS_THIN_CW(M)                                                                                    \
+  case kRoute_thin_cout_wgrad_t##M:                                                                         \
+    if (!ensure_dynamic_lds((const void*)thin_cout_wgrad_kernel<M>, lds)) return SE3DS_E_LAUNCH;            \
+    SE3DS_LAUNCH(thin_cout_wgrad_t##M, thin_cout_wgrad_kernel<M>, dim3((unsigned)c.splits),                 \
+                 dim3(kThinWThreads), lds, s, q);                                                           \
+    break;
+  switch (c.route) {   // column tiles per wave
+    SE3DS_THIN_CW(2) SE3DS_THIN_CW(3) SE3DS_THIN_CW(4)
+    default: SE3DS_THIN_CW(5)
+  }
 #undef SE3DS_THIN_CW
-    const int64_t tnel = (int64_t)9 * cin * cout;
-    launch_wgrad_reduce((const float*)workspace, (int)blocks, tnel, accumulate, nullptr, dw, s);
-    return check_launch("conv2d_wgrad(thin cout)");
-  }
-  if (dtype == SE3DS_BF16) {
-    int tsteps = 0;
-    const int tsplits = wgrad_taps_thin_splits(n, h, w, cin, cout, k, &tsteps);
-    if (tsplits > 0) {
-      hipStream_t s = as_stream(stream);
-      const int64_t px = (int64_t)n * h * w;
-      uint16_t* dyp = (uint16_t*)workspace;
-      float* part = (float*)((char*)workspace + ((size_t)px * 16 + 255) / 256 * 256);
-      SE3DS_LAUNCH(pad_channels8, pad_channels8_kernel, dim3(grid_for(px, 256)), dim3(256), 0, s,
-                   (const uint16_t*)dy, cout, px, dyp);
-      WgradTapsParams q;
-      q.x = (const uint16_t*)x; q.H = h; q.W = w; q.Cin = cin;
-      q.dy = dyp; q.Ho = h; q.Wo = w; q.Cout = cout;
-      q.N = n; q.pad_t = pad; q.pad_l = pad; q.wrap_w = 0; q.src_mask = nullptr;
-      q.dw = part;
-      q.steps_y = ceil_div(h, 2); q.steps_x = ceil_div(w, 32);
-      q.total_steps = tsteps;
-      q.steps_per_split = ceil_div(tsteps, tsplits);
-      q.dy_cstride = 8; q.co_valid = cout;
-      dim3 tgrid((unsigned)(cin / 64), 1, (unsigned)tsplits);
-      SE3DS_LAUNCH(wgrad_taps_thin, wgrad_taps_kernel, tgrid, dim3(512), 0, s, q);
-      const int64_t tnel = (int64_t)9 * cin * cout;
-      launch_wgrad_reduce((const float*)part, tsplits, tnel, accumulate, nullptr, dw, s);
-      return check_launch("conv2d_wgrad(taps, thin)");
-    }
-  }
-  // tmp[(ky',kx'),co,ci] = wgrad of the conv with input dy (cout channels), output-grad x
-  float* tmp = (float*)workspace;
-  const size_t tmp_bytes = (sizeof(float) * (size_t)k * k * cin * cout + 63) / 64 * 64;
-  int rc = se3ds_conv2d_wgrad(dy, x, tmp, dtype, n, h, w, cout, h, w, cin, k, k, 1, k - 1 - pad,
-                              k - 1 - pad, 0, nullptr, 0, nullptr, nullptr, 0,
-                              (char*)workspace + tmp_bytes, workspace_bytes - tmp_bytes, stream);
-  if (rc != SE3DS_OK) return rc;
-  SE3DS_LAUNCH(wgrad_swap_fixup, wgrad_swap_fixup_kernel,
-               dim3(grid_for((int64_t)k * k * cin * cout, 256)), dim3(256), 0, as_stream(stream),
-               tmp, k, cin, cout, accumulate, dw);
-  return check_launch("conv2d_wgrad_swapped");
+  launch_wgrad_reduce(part, c.splits, nel, accumulate, nullptr, dw, s);
+  return check_launch("conv2d_wgrad(thin cout)");
 }
 
 // Test hooks, host only: which kernel instantiation the calling thread's dispatchers launched last

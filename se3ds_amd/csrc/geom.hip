@@ -8,9 +8,7 @@
 // citations in include/se3ds_hip.h).  Index math lives in include/se3ds_geom_math.h and is
 // shared bit-for-bit with the CPU oracle.  Built with -ffp-contract=off.
 #include <atomic>
-#include <mutex>
 #include <type_traits>
-#include <unordered_map>
 
 #include "common.h"
 #include "../../include/se3ds_geom_math.h"
@@ -2710,19 +2708,6 @@ splat_sort_resolve_kernel(int height, int width, int nsuper, int super_x, int su
   }
 }
 
-// (set once per kernel and size: hipFuncSetAttribute on every launch is host time for nothing)
-inline bool sort_lds_attr(const void* fn, size_t bytes) {
-  static std::mutex mu;
-  static std::unordered_map<const void*, size_t> done;
-  std::lock_guard<std::mutex> lock(mu);
-  auto it = done.find(fn);
-  if (it != done.end() && it->second >= bytes) return true;
-  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
-    return false;
-  done[fn] = bytes;
-  return true;
-}
-
 template <typename T, bool EQUIRECT, int C, int PTS>
 int launch_splat_sorted_c(const float* coords, const float* offset, const T* feats, int n, int64_t m,
                           int64_t ld, int height, int width, float depth_scale, float input_void,
@@ -2738,7 +2723,7 @@ int launch_splat_sorted_c(const float* coords, const float* offset, const T* fea
   const void* k1 = dbg ? (const void*)splat_sort_kernel<T, EQUIRECT, C, true, PTS>
                        : (const void*)splat_sort_kernel<T, EQUIRECT, C, false, PTS>;
   const void* k2 = (const void*)splat_sort_resolve_kernel<C>;
-  if (!sort_lds_attr(k1, lds1) || !sort_lds_attr(k2, lds2)) return SE3DS_E_LAUNCH;
+  if (!ensure_dynamic_lds(k1, lds1) || !ensure_dynamic_lds(k2, lds2)) return SE3DS_E_LAUNCH;
   if (dbg)
     hipLaunchKernelGGL((splat_sort_kernel<T, EQUIRECT, C, true, PTS>), g_pt, dim3(kSThreads), lds1,
                        stream, coords, offset, feats, m, ld, height, width, wmagic, input_void,
