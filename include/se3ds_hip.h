@@ -840,6 +840,50 @@ int se3ds_png_encode_planes(const int64_t* table, const int64_t* host_table, int
 size_t se3ds_png_encode_planes_workspace_bytes(const int64_t* host_table, int n);
 int64_t se3ds_png_encode_planes_out_bytes(const int64_t* host_table, int n);
 
+/* Baseline JPEG encoding of many uint8 images: the entropy-coded data of the files libjpeg's default
+ * encoder writes (Pillow's Image.save(f, 'JPEG', quality=q, subsampling=s)), byte for byte:
+ * 16-bit colour conversion, box downsampling, slow-integer forward DCT, rounded-division
+ * quantisation, the Annex K Huffman tables, restart intervals.  csrc/jpeg_encode.hip, arithmetic
+ * in csrc/jpeg_encode_core.h.  The caller adds the container (utils/jpeg.py jpeg_container).
+ * table: device int64 [n][se3ds_jpeg_encode_fields() = 48], `struct Image` of jpeg_encode_core.h:
+ * device pointer of the pixels (height x width x components uint8, dense), width, height,
+ * components (1: a grey file; 3: RGB -> YCbCr), luma sampling h, v (1x1, 2x1 or 2x2; grey 1x1;
+ * chroma is 1x1), restart interval in MCUs (0: none), blocks of the images in front (a running
+ * sum from 0; an image has mcus_x * mcus_y * (1 or h * v + 2) blocks), transform tiles of the
+ * images in front (a running sum from 0; a tile is up to se3ds_jpeg_encode_tile_blocks() / blocks
+ * per MCU consecutive MCUs of one MCU row, so an image has mcus_y * ceil(mcus_x / that) tiles), 7
+ * reserved, then the luma
+ * and the chroma quantisation table, uint16 [2][64] in row-major order, every entry 1..255.
+ * out: the images' entropy-coded bytes (stuffed, RSTn markers between the segments, every
+ * segment's last byte padded with 1 bits), one image behind the other without gaps; sizes_dev:
+ * int64 [n + 1], image i's bytes are out[sizes_dev[i] .. sizes_dev[i + 1]).
+ * workspace: device, 16-byte aligned, at least se3ds_jpeg_encode_workspace_bytes(host_table, n)
+ * bytes (0: the table is not valid); out: at least se3ds_jpeg_encode_out_bytes(host_table, n), a
+ * worst-case bound (every block 1660 bits, every byte stuffed).
+ * host_table: the HOST copy of the table, validated before anything runs (BADSHAPE: n < 1 or >
+ * 65535, a null pointer, a size < 1, components outside {1, 3}, a restart interval outside
+ * 0..65535, a quantiser outside 1..255, a running sum that is not the one above, an out buffer
+ * that is too small; UNSUPPORTED: a size above 65535, any other sampling; WORKSPACE: a workspace
+ * that is too small).
+ * phases: 15 = everything, what callers pass; 1 = the transform (pixels -> quantised coefficients),
+ * 2 = measure (every block's Huffman bits, kept, and the scan that places them; groups of
+ * se3ds_jpeg_encode_scan_group_blocks() blocks), 4 = pack, count (units of
+ * se3ds_jpeg_encode_pack_unit_blocks() blocks: assemble, count the stuffing, scan), 8 = pack, write
+ * (assemble again, stuff, store); a later phase needs the workspace the earlier ones filled for the
+ * same table (tools/jpeg_encode_bench.py times
+ * them apart).  Six launches on `stream`, no host synchronisation, no global atomics, integer
+ * arithmetic: the output is the same bytes on every run. */
+int se3ds_jpeg_encode(const int64_t* table, const int64_t* host_table, int n, uint8_t* workspace,
+                      int64_t workspace_bytes, uint8_t* out, int64_t out_bytes, int64_t* sizes_dev,
+                      int phases, void* stream);
+size_t se3ds_jpeg_encode_workspace_bytes(const int64_t* host_table, int n);
+int64_t se3ds_jpeg_encode_out_bytes(const int64_t* host_table, int n);
+int se3ds_jpeg_encode_fields(void);
+int se3ds_jpeg_encode_scan_group_blocks(void);
+int se3ds_jpeg_encode_pack_unit_blocks(void);
+int se3ds_jpeg_encode_block_words(void);
+int se3ds_jpeg_encode_tile_blocks(void);
+
 /* ======================================================================================
  * Writing training records -- the inverse of datasets/indoor_datasets.py:125-247.
  * csrc/records.hip, datasets/record_writer.py.

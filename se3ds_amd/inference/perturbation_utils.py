@@ -235,3 +235,25 @@ def perturbation_augment(model, num_samples, start_pos, depth, xy_perturb=1.5, z
       images.append(model.predict_views(positions[s:s + views_per_forward]).pred_rgb)
   return Augmentation(images=torch.cat(images, dim=0), positions=positions, offsets=offsets,
                       proportion_invalid=np.asarray(proportions, np.float64), num_drawn=num_drawn)
+
+
+def save_augmentation(aug: Augmentation, directory, prefix='aug', quality=90, subsampling='4:2:0'):
+  """Writes what `perturbation_augment` returned the way a VLN training set stores panoramas:
+  `<prefix>_<i>.jpg` for every image, all encoded on the device in one call
+  (utils.jpeg.encode_jpeg_batch), and `<prefix>.npz` with positions, offsets, proportion_invalid and
+  num_drawn.  Every file is written under a temporary name, synced and renamed
+  (npz_writer.write_bytes_atomic), so a reader never sees a partial one.  Returns the paths, the images' first and the .npz last."""
+  import os
+  from se3ds_amd.utils import jpeg, npz_writer
+  files = jpeg.encode_jpeg_batch(list(aug.images), quality=quality, subsampling=subsampling)
+  os.makedirs(directory, exist_ok=True)
+  paths = []
+  for i, data in enumerate(files):
+    path = os.path.join(directory, f'{prefix}_{i}.jpg')
+    npz_writer.write_bytes_atomic(path, data)
+    paths.append(path)
+  path = os.path.join(directory, f'{prefix}.npz')
+  npz_writer.savez(path, {
+      'positions': aug.positions.detach().cpu().numpy(), 'offsets': np.asarray(aug.offsets),
+      'proportion_invalid': np.asarray(aug.proportion_invalid), 'num_drawn': np.asarray(aug.num_drawn, np.int64)})
+  return paths + [path]

@@ -1,12 +1,16 @@
-"""Baseline JPEG files -> uint8 pixels on the device, without TensorFlow or an image library: the
-`tf.image.decode_jpeg(rgb.jpeg)` the VLN augmentation notebook starts from, and the container
-Matterport panoramas are distributed in.
+"""Baseline JPEG files <-> uint8 pixels on the device, without TensorFlow or an image library: the
+`tf.image.decode_jpeg(rgb.jpeg)` the VLN augmentation notebook starts from, the container
+Matterport panoramas are distributed in, and the files the augmentation writes back.
 
   parse_jpeg         the container on the host (NumPy): SOF0 / SOF1 at 8 bits, DQT, DHT, DRI, one
                      interleaved SOS; the entropy segments are found, nothing is decoded.
   decode_jpeg_batch  files of any mix of geometries -> one upload, one `se3ds_jpeg_decode`
                      (csrc/jpeg.hip: speculative parallel Huffman decode per restart interval,
                      slow-integer inverse DCT, fancy upsampling, colour), tensors (H, W, C) uint8.
+  encode_jpeg_batch  uint8 tensors of any mix of sizes -> the files libjpeg's default encoder writes
+                     (Pillow's Image.save at the same quality and subsampling), byte for byte: one
+                     `se3ds_jpeg_encode` (csrc/jpeg_encode.hip), the container (`jpeg_container`,
+                     `quality_tables`) on the host.
 
 The arithmetic is libjpeg's defaults (JDCT_ISLOW, fancy upsampling), which `tf.image.decode_jpeg`
 documents as its defaults too; the tests pin it against Pillow.  Where a sample leaves [0, 255]
@@ -14,6 +18,7 @@ before the clamp by more than a decoder's look-up table covers, this decoder sat
 
 There is no CPU fallback: a non-CUDA device raises Se3dsHipError."""
 import enum
+import struct
 from typing import List, NamedTuple, Sequence, Tuple, Union
 
 import numpy as np
@@ -379,3 +384,194 @@ def decode_jpeg_batch(bufs: Sequence[Union[bytes, JpegScan]], device, channels: 
     return batch.out, pending
   pending.check()
   return batch.out
+
+
+# ------------------------------------------------------------------------------ encoding
+# ITU-T T.81 Annex K.1, K.2: the quantisation tables libjpeg scales, row-major order
+_LUMA_QUANT = np.array([16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57,
+                        69, 56, 14, 17, 22, 29, 51, 87, 80, 62, 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55,
+                        64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103,
+                        99], np.int64)
+_CHROMA_QUANT = np.array([17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99,
+                          99, 99, 47, 66, 99, 99, 99, 99, 99, 99] + [99] * 32, np.int64)
+# Annex K.3: (counts per code length 1..16, values) of DC luma, AC luma, DC chroma, AC chroma
+_AC_VALUES = (
+    '01 02 03 00 04 11 05 12 21 31 41 06 13 51 61 07 22 71 14 32 81 91 a1 08 23 42 b1 c1 15 52 d1 f0 24 33 62 72 '
+    '82 09 0a 16 17 18 19 1a 25 26 27 28 29 2a 34 35 36 37 38 39 3a 43 44 45 46 47 48 49 4a 53 54 55 56 57 58 59 '
+    '5a 63 64 65 66 67 68 69 6a 73 74 75 76 77 78 79 7a 83 84 85 86 87 88 89 8a 92 93 94 95 96 97 98 99 9a a2 a3 '
+    'a4 a5 a6 a7 a8 a9 aa b2 b3 b4 b5 b6 b7 b8 b9 ba c2 c3 c4 c5 c6 c7 c8 c9 ca d2 d3 d4 d5 d6 d7 d8 d9 da e1 e2 '
+    'e3 e4 e5 e6 e7 e8 e9 ea f1 f2 f3 f4 f5 f6 f7 f8 f9 fa',
+    '00 01 02 03 11 04 05 21 31 06 12 41 51 07 61 71 13 22 32 81 08 14 42 91 a1 b1 c1 09 23 33 52 f0 15 62 72 d1 '
+    '0a 16 24 34 e1 25 f1 17 18 19 1a 26 27 28 29 2a 35 36 37 38 39 3a 43 44 45 46 47 48 49 4a 53 54 55 56 57 58 '
+    '59 5a 63 64 65 66 67 68 69 6a 73 74 75 76 77 78 79 7a 82 83 84 85 86 87 88 89 8a 92 93 94 95 96 97 98 99 9a '
+    'a2 a3 a4 a5 a6 a7 a8 a9 aa b2 b3 b4 b5 b6 b7 b8 b9 ba c2 c3 c4 c5 c6 c7 c8 c9 ca d2 d3 d4 d5 d6 d7 d8 d9 da '
+    'e2 e3 e4 e5 e6 e7 e8 e9 ea f2 f3 f4 f5 f6 f7 f8 f9 fa')
+HUFFMAN_TABLES = (
+    (0x00, bytes([0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0]), bytes(range(12))),
+    (0x10, bytes([0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d]), bytes.fromhex(_AC_VALUES[0])),
+    (0x01, bytes([0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0]), bytes(range(12))),
+    (0x11, bytes([0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77]), bytes.fromhex(_AC_VALUES[1])),
+)
+_SUBSAMPLING = {'4:4:4': (1, 1), '4:2:2': (2, 1), '4:2:0': (2, 2)}
+
+
+def quality_tables(quality: int) -> Tuple[np.ndarray, np.ndarray]:
+  """(luma, chroma) quantisation tables, int64 (64,) in row-major order, of libjpeg's
+  jpeg_set_quality(quality, force_baseline=TRUE): the Annex K tables times 5000 / q percent below
+  50 and 200 - 2 q percent from 50 on, rounded, clamped to 1..255."""
+  q = _quality(quality)
+  scale = 5000 // q if q < 50 else 200 - 2 * q
+  return tuple(np.clip((base * scale + 50) // 100, 1, 255) for base in (_LUMA_QUANT, _CHROMA_QUANT))
+
+
+def _quality(q) -> int:
+  if isinstance(q, bool) or not isinstance(q, (int, np.integer)) or not 1 <= int(q) <= 100:
+    raise ValueError(f'quality: an int 1..100, got {q!r}')
+  return int(q)
+
+
+def _marker_segment(marker: int, body: bytes) -> bytes:
+  return bytes([0xFF, marker]) + struct.pack('>H', 2 + len(body)) + body
+
+
+def jpeg_container(height: int, width: int, components: int, h0: int, v0: int, tables, restart_interval: int,
+                   entropy_coded: bytes) -> bytes:
+  """The file around the entropy-coded bytes of se3ds_jpeg_encode, as libjpeg lays it out: SOI, APP0
+  (JFIF 1.01, density 1 x 1 without unit, no thumbnail), one DQT per table, SOF0 (components 1, 2,
+  3; luma h0 x v0, chroma 1 x 1 on table 1), DHT for DC 0, AC 0, DC 1, AC 1 (the first two alone for
+  grey), DRI if the interval is not 0, SOS, the data, EOI.  tables: (luma, chroma) in row-major
+  order."""
+  if components not in (1, 3) or (components == 1 and (h0, v0) != (1, 1)):
+    raise ValueError(f'jpeg_container: {components} component(s) at sampling {h0} x {v0}')
+  out = [b'\xff\xd8', _marker_segment(0xE0, b'JFIF\0' + bytes([1, 1, 0, 0, 1, 0, 1, 0, 0]))]
+  for tq in range(2 if components == 3 else 1):
+    out.append(_marker_segment(0xDB, bytes([tq]) + bytes(int(v) for v in np.asarray(tables[tq])[ZIGZAG])))
+  out.append(_marker_segment(0xC0, struct.pack('>BHHB', 8, height, width, components) + b''.join(
+      bytes([i + 1, ((h0 << 4) | v0) if i == 0 else 0x11, min(i, 1)]) for i in range(components))))
+  for tag, counts, values in HUFFMAN_TABLES[:2 * min(components, 2)]:
+    out.append(_marker_segment(0xC4, bytes([tag]) + counts + values))
+  if restart_interval:
+    out.append(_marker_segment(0xDD, struct.pack('>H', restart_interval)))
+  out.append(_marker_segment(0xDA, bytes([components]) + b''.join(
+      bytes([i + 1, 0x11 * min(i, 1)]) for i in range(components)) + b'\x00\x3f\x00'))
+  return b''.join(out) + bytes(entropy_coded) + b'\xff\xd9'
+
+
+class EncodeSpec(NamedTuple):
+  """What one image of encode_jpeg_batch becomes: geometry, sampling, tables, restart interval."""
+  height: int
+  width: int
+  components: int
+  h0: int
+  v0: int
+  tables: Tuple[np.ndarray, np.ndarray]
+  restart_interval: int
+
+  @property
+  def blocks(self):
+    mcus = -(-self.width // (8 * self.h0)) * -(-self.height // (8 * self.v0))
+    return mcus * (1 if self.components == 1 else self.h0 * self.v0 + 2)
+
+
+def encode_specs(shapes, dtypes, quality=75, subsampling='4:2:0', restart_interval=0) -> List[EncodeSpec]:
+  """The argument checks of encode_jpeg_batch (no device needed): ValueError naming the argument."""
+  n = len(shapes)
+  if isinstance(quality, (list, tuple, np.ndarray)):
+    if len(quality) != n:
+      raise ValueError(f'quality: {len(quality)} entries for {n} images')
+    qualities = [_quality(q) for q in quality]
+  else:
+    qualities = [_quality(quality)] * n
+  if subsampling not in _SUBSAMPLING:
+    raise ValueError(f"subsampling: '4:4:4', '4:2:2' or '4:2:0', got {subsampling!r}")
+  row = restart_interval == 'row'
+  if not row and (isinstance(restart_interval, bool) or not isinstance(restart_interval, (int, np.integer)) or
+                  not 0 <= int(restart_interval) <= 65535):
+    raise ValueError(f"restart_interval: MCUs 0..65535 or 'row', got {restart_interval!r}")
+  specs = []
+  for shape, dtype, q in zip(shapes, dtypes, qualities):
+    if len(shape) != 3 or shape[2] not in (1, 3) or shape[0] < 1 or shape[1] < 1 or dtype != torch.uint8:
+      raise ValueError(f'images: uint8 (H,W,1) or (H,W,3) expected, got {dtype} {tuple(shape)}')
+    if shape[0] > 65535 or shape[1] > 65535:
+      raise ValueError(f'images: a JPEG file holds at most 65535 x 65535 pixels, got {tuple(shape)}')
+    h0, v0 = (1, 1) if shape[2] == 1 else _SUBSAMPLING[subsampling]
+    interval = -(-int(shape[1]) // (8 * h0)) if row else int(restart_interval)
+    specs.append(EncodeSpec(int(shape[0]), int(shape[1]), int(shape[2]), h0, v0, quality_tables(q), interval))
+  return specs
+
+
+class JpegEncodeBatch:
+  """The table, the workspace and the output buffer of one batch on the current stream of the
+  images' device: `launch(phases)` queues `se3ds_jpeg_encode` (the timing tool launches the phases
+  apart), `files()` reads the sizes and then the bytes in use back and adds the containers."""
+
+  def __init__(self, images: Sequence[torch.Tensor], specs: Sequence[EncodeSpec]):
+    L = _lib.lib()
+    n = len(images)
+    self.images, self.specs, self.device = images, specs, images[0].device
+    table = np.zeros((n, L.se3ds_jpeg_encode_fields()), np.int64)
+    blocks = tiles = 0
+    tile_blocks = L.se3ds_jpeg_encode_tile_blocks()
+    for i, (x, s) in enumerate(zip(images, specs)):
+      table[i, :9] = (x.data_ptr(), s.width, s.height, s.components, s.h0, s.v0, s.restart_interval, blocks, tiles)
+      table[i, 16:].view(np.uint16)[:] = np.concatenate(s.tables)
+      blocks += s.blocks
+      mcus_x, mcus_y = -(-s.width // (8 * s.h0)), -(-s.height // (8 * s.v0))
+      tiles += mcus_y * -(-mcus_x // (tile_blocks // (s.blocks // (mcus_x * mcus_y))))
+    self.table = table
+    self.workspace_bytes = L.se3ds_jpeg_encode_workspace_bytes(table.ctypes.data, n)
+    self.out_bytes = L.se3ds_jpeg_encode_out_bytes(table.ctypes.data, n)
+    with torch.cuda.device(self.device):
+      self.table_dev, _ = upload([table], self.device)
+      self.workspace = torch.empty((max(self.workspace_bytes, 16),), dtype=torch.uint8, device=self.device)
+      self.out = torch.empty((max(self.out_bytes, 16),), dtype=torch.uint8, device=self.device)
+      self.sizes = torch.empty((n + 1,), dtype=torch.int64, device=self.device)
+
+  def launch(self, phases: int = 15) -> None:
+    with torch.cuda.device(self.device):
+      rc = _lib.lib().se3ds_jpeg_encode(
+          _lib.ptr(self.table_dev), self.table.ctypes.data, len(self.table), _lib.ptr(self.workspace),
+          self.workspace_bytes, _lib.ptr(self.out), self.out_bytes, _lib.ptr(self.sizes), phases, _lib.stream())
+    _lib.check(rc, 'se3ds_jpeg_encode')
+
+  def entropy_coded(self) -> List[bytes]:
+    """Every image's bytes between the SOS header and EOI.  The output buffer is a worst-case bound,
+    so the n + 1 offsets come back first and then only the bytes in use."""
+    starts = Readback(self.sizes).wait()
+    data = Readback(self.out[:max(int(starts[-1]), 1)]).wait()
+    return [data[int(a):int(b)].tobytes() for a, b in zip(starts[:-1], starts[1:])]
+
+  def files(self) -> List[bytes]:
+    return [jpeg_container(s.height, s.width, s.components, s.h0, s.v0, s.tables, s.restart_interval, data)
+            for s, data in zip(self.specs, self.entropy_coded())]
+
+
+def encode_jpeg_batch(images: Sequence[torch.Tensor], quality=75, subsampling='4:2:0', restart_interval=0,
+                      device=None) -> List[bytes]:
+  """uint8 device tensors (H,W,1|3), any mix of sizes -> their baseline JPEG files, the bytes Pillow's
+  Image.save(f, 'JPEG', quality=q, subsampling=s) writes: one upload (the table), the launches of
+  `se3ds_jpeg_encode` (csrc/jpeg_encode.hip: transform, measure + scan, pack), the offsets and the
+  packed bytes back; the host adds the container (jpeg_container).
+  quality: an int 1..100 or a sequence with one per image.  subsampling: '4:4:4', '4:2:2' or
+  '4:2:0'; a one-channel image is a grey file and ignores it.  restart_interval: MCUs per restart
+  interval, 0 = none, 'row' = one MCU row (a file whose segments decode_jpeg_batch spreads over
+  workgroups).  device: where the tensors must be (None: where the first one is).  Bad arguments
+  raise ValueError naming the argument; a non-CUDA tensor raises Se3dsHipError: there is no CPU
+  encoder.
+  Memory: the workspace (346 B a block) and the output buffer (416 B a block, every block at its
+  longest and every byte stuffed) are sized for the worst case and allocated per call: 0.15 GB for
+  one 2048 x 4096 image at 4:2:0, 1.35 GB for nine of them, to emit a few MB.  Only the bytes in
+  use come back: the n + 1 offsets first, then out[:offsets[n]]."""
+  images = list(images)
+  if not images:
+    return []
+  specs = encode_specs([x.shape for x in images], [x.dtype for x in images], quality, subsampling,
+                       restart_interval)
+  dev = images[0].device if device is None else torch.device(device)
+  for x in images:
+    if x.device.type != dev.type or (dev.index is not None and x.device.index != dev.index):
+      raise ValueError(f'images: a tensor on {x.device} in a batch on {dev}')
+  _lib.require_cuda(*images)
+  batch = JpegEncodeBatch([x.contiguous() for x in images], specs)
+  batch.launch(15)
+  return batch.files()

@@ -1,22 +1,33 @@
 """The reference's utils/logger.UniversalLogger without TensorFlow: scalars and image grids go to
 a TensorBoard event file (utils/tf_events.py) and, for scalars, to the log.  Images are PNG-encoded
-on the device in one batch per call (utils/png.encode_png_batch), or on the host for NumPy arrays."""
+on the device in one batch per call (utils/png.encode_png_batch), or on the host for NumPy arrays;
+image_format='jpeg' writes baseline JPEG instead (utils/jpeg.encode_jpeg_batch, device only)."""
 import logging
 from typing import Callable, Optional
 
 import numpy as np
 
-from se3ds_amd.utils import png, tf_events
+from se3ds_amd.utils import jpeg, png, tf_events
 
 
 class UniversalLogger:
   """Constructor surface of the reference (:36-55) plus `encoder`: 'device' takes uint8 device
-  tensors, 'host' NumPy arrays (a CPU-only process can write summaries)."""
+  tensors, 'host' NumPy arrays (a CPU-only process can write summaries), and `image_format`: 'png'
+  (the default) or 'jpeg' at `jpeg_quality`, 4:2:0, which needs encoder='device'; a one-channel
+  image becomes a grey file."""
 
   def __init__(self, workdir: str, step: int, num_train_steps: Optional[int] = None,
-               logging_fn: Optional[Callable[[str], None]] = None, encoder: str = 'device'):
+               logging_fn: Optional[Callable[[str], None]] = None, encoder: str = 'device',
+               image_format: str = 'png', jpeg_quality: int = 90):
     if encoder not in ('host', 'device'):
       raise ValueError(f"encoder: 'host' or 'device', got {encoder!r}")
+    if image_format not in ('png', 'jpeg'):
+      raise ValueError(f"image_format: 'png' or 'jpeg', got {image_format!r}")
+    if image_format == 'jpeg' and encoder != 'device':
+      raise ValueError("image_format: 'jpeg' is encoded on the device only (encoder='device')")
+    if image_format == 'jpeg':
+      jpeg.quality_tables(jpeg_quality)   # ValueError naming quality
+    self.image_format, self.jpeg_quality = image_format, jpeg_quality
     self.summary_writer = tf_events.EventFileWriter(workdir)
     self.encoder = encoder
     self._num_train_steps = num_train_steps
@@ -47,7 +58,9 @@ class UniversalLogger:
         images.append(value[i])
     if not images:
       return
-    if self.encoder == 'device':
+    if self.image_format == 'jpeg':
+      files = jpeg.encode_jpeg_batch(images, quality=self.jpeg_quality)
+    elif self.encoder == 'device':
       files = png.encode_png_batch(images)
     else:
       files = [png.encode_png_host(x) for x in images]

@@ -123,6 +123,22 @@ def write_npz(path, members, force_zip64=False):
     raise
 
 
+def write_bytes_atomic(path, data) -> None:
+  """`data` to `path` the way write_npz lands its file: `<path>.tmp`, fsync, `os.replace`; on an
+  exception the temporary file is removed."""
+  tmp = path + '.tmp'
+  try:
+    with open(tmp, 'wb') as f:
+      f.write(data)
+      f.flush()
+      os.fsync(f.fileno())
+    os.replace(tmp, path)
+  except BaseException:
+    if os.path.exists(tmp):
+      os.remove(tmp)
+    raise
+
+
 def savez(path, arrays, force_zip64=False):
   """`np.savez(path, **arrays)` through this writer, checksums from zlib: the same member names and
   arrays."""
