@@ -678,6 +678,38 @@ int se3ds_video_transform(const float* image, const uint8_t* segmentation,
                           int h, int w, float* o_original, float* o_image, uint8_t* o_seg,
                           uint8_t* o_pd_seg, float* o_depth, float* o_pd_depth, void* stream);
 
+/* datasets/indoor_datasets.py:420-450, the reduction in front of the RE10K crop: per example the
+ * first and last row and the first and last column of visible_mask uint8 (N,H0,W0) that hold a
+ * nonzero pixel, into extents int32 [N][4] = r0, r1, c0, c1 by integer atomic min / max
+ * (deterministic).  The CALLER initialises extents to H0, -1, W0, -1 (any r0 > r1 reads as "no
+ * visible pixel"); it does so in the upload that carries the draw rows, so there is no memset.
+ * 16 bytes a lane when W0 and the plane's address are multiples of 16, a byte a lane otherwise;
+ * se3ds_re10k_extent_vector_bytes (host only) tells which. */
+int se3ds_re10k_extent(const uint8_t* visible_mask, int n, int h0, int w0, int32_t* extents,
+                       void* stream);
+int se3ds_re10k_extent_vector_bytes(const uint8_t* visible_mask, int w0);
+
+/* datasets/indoor_datasets.py:377-535 (_transform_fn_re10k) + :553-597 on decoded frames resident
+ * in HBM, one gather: convert_image_dtype (:185-228), blurred = 1 - (visible_mask > 0) (:238), band
+ * masking of proj_mask on the raw grid (:389-412), the crop box from `extents` and the draws
+ * (:445-472, csrc/re10k_box_core.h), crop, bilinear + clip (image) / nearest (everything else,
+ * proj_image included) resize of the CROP to (h, w) (:486-491), proj_image *= proj_mask and
+ * proj_depth *= proj_mask (:577-585).  iparams [N][3] = hmode (0 none / 1 start<x<end / 2 x>start
+ * or x<end), vmode (0 / 1), crop flag; fparams [N][7] = hstart, hend, vstart, vend (raw-grid
+ * pixels), pad, x_shift, y_shift.  An example whose crop flag is 0 takes the whole frame as its
+ * box: with (h, w) = (h0, w0) that is conversion, band masks and batch transform only (:474).
+ * o_bbox int32 [N][4] = x_min, y_min, x_max, y_max (:520); o_status int32 [N] = 0 ok / 1 no
+ * visible pixel / 2 the box does not lie inside the frame; such an example's outputs are zeros.
+ * No status and no draw makes the kernel read outside a plane.  extents and o_bbox may be NULL
+ * together: no example is cropped, the flags are ignored.  Any other NULL is BADSHAPE. */
+int se3ds_re10k_transform(const uint8_t* image, const uint8_t* proj_image, const uint16_t* depth,
+                          const uint16_t* proj_depth, const uint8_t* proj_mask,
+                          const uint8_t* visible_mask, const uint8_t* segmentation,
+                          const int32_t* extents, const int32_t* iparams, const float* fparams,
+                          int n, int h0, int w0, int h, int w, float* o_image, float* o_proj_image,
+                          float* o_proj_mask, float* o_proj_depth, float* o_depth, float* o_blurred,
+                          int32_t* o_seg, int32_t* o_bbox, int32_t* o_status, void* stream);
+
 /* PNG reconstruction (un-filtering) of a whole batch in one launch -- the second half of
  * tf.image.decode_png (datasets/indoor_datasets.py:185-228); the host or se3ds_png_inflate
  * inflates.  csrc/png.hip.

@@ -7,8 +7,11 @@ utils/tf_records.py, `input_fn` (datasets/base_dataset.py:105-150) lists, repeat
 batches them, and utils/png.py decodes the seven PNGs of every example -- inflate on a small host
 thread pool (or, with inflate='device', in one launch of `se3ds_png_inflate`), reconstruction of the
 whole batch in one launch (`se3ds_png_unfilter`).  TensorFlow is
-not needed.  Not built: sharding over several input pipelines beyond the seed offset, `cache`, the
-RE10K records (`visible_mask`, `_transform_fn_re10k`).
+not needed.  `RE10KImageDataset` reads the RE10K records (`visible_mask`, :232-240) and runs
+`_transform_fn_re10k` (:377-535): the extents of the visible pixels are reduced on the device
+(`se3ds_re10k_extent`) and the crop box is evaluated inside the gather (`se3ds_re10k_transform`).
+Not built: sharding over several input pipelines beyond the seed offset, `cache`, batches that mix
+MP3D and RE10K records.
 
 Same constructor arguments and gin selectors as the reference (`R2RImageDataset.image_size`, ...).
 The random draws follow the statement order of `_transform_fn` and are made on the host with a
@@ -33,7 +36,7 @@ from se3ds_amd import _lib
 from se3ds_amd import constants
 from se3ds_amd import gin_lite as gin
 from se3ds_amd.utils import png
-from se3ds_amd.utils._staging import cuda_device
+from se3ds_amd.utils._staging import Readback, cuda_device
 from se3ds_amd.utils import tf_records
 from se3ds_amd.utils.tf_records import FixedLenFeature
 
@@ -98,6 +101,10 @@ class R2RImageDataset:
     self.pad_minval = pad_minval
     self.pad_maxval = pad_maxval
     self.re_10k_crop = re_10k_crop
+
+  # what `_parse` decodes and `input_fn` batches; RE10KImageDataset has its own tables
+  RAW_DTYPES = RAW_DTYPES
+  IMAGE_PLANES = IMAGE_PLANES
 
   # ------------------------------------------------------------------------------ the draws
   def draw_params(self, rng: np.random.Generator, height: int, width: int) -> dict:
@@ -176,6 +183,14 @@ class R2RImageDataset:
     n, h0, w0 = raw['proj_mask'].shape
     return self.device_transform(raw, [self.draw_params(rng, h0, w0) for _ in range(n)])
 
+  def _transform_examples(self, examples: List[dict], raw: Dict[str, torch.Tensor],
+                          params: List[dict]):
+    """input_fn's transform of one decoded batch: -> (batch, status).  status: None, or an object
+    whose `check()` waits for a per-example status the launch left on the device and raises
+    ValueError -- input_fn calls it just before it yields the batch."""
+    del examples
+    return self.device_transform(raw, params), None
+
   # --------------------------------------------------------------------------- TFRecord input
   def _features(self) -> Dict[str, FixedLenFeature]:
     """The feature spec of the reference's `_parse` (:149-178)."""
@@ -202,13 +217,18 @@ class R2RImageDataset:
     (RGB for the two images, 16-bit grey for the two depths, 8-bit grey for the rest: no channel
     conversion is built).  `segmentation_valid` (:222-223) is left out: nothing in the reference's
     trainer or here reads it.  Records of DatasetType.RE10K raise NotImplementedError
-    (`visible_mask` is not built)."""
+    (`RE10KImageDataset` reads them)."""
     ex = tf_records.apply_features(tf_records.parse_example(record), self._features())
     if ex['dataset_type'] == DatasetType.RE10K.value:
       raise NotImplementedError('RE10K records (visible_mask, _transform_fn_re10k) are not supported')
+    return self._parsed(ex, inflate)
+
+  def _parsed(self, ex: dict, inflate: str) -> dict:
+    """The planes of self.IMAGE_PLANES and the scalars of one Example that `_features` was applied
+    to: the body of `_parse`."""
     h, w = self.preprocessed_image_height, 2 * self.preprocessed_image_height
     out = dict(dataset_type=np.int64(ex['dataset_type']))
-    for name, (feature, channels, depth) in IMAGE_PLANES.items():
+    for name, (feature, channels, depth) in self.IMAGE_PLANES.items():
       try:
         plane = (png.parse_png if inflate == 'host' else png.parse_png_container)(ex[feature])
       except (ValueError, NotImplementedError) as e:
@@ -321,14 +341,15 @@ class R2RImageDataset:
       return None   # the remainder is dropped
 
     def finish(examples, raw):
+      """-> the batch and its unchecked status (`_transform_examples`)."""
       params = [self.draw_params(draw_rng, h0, w0) for _ in examples]
-      batch = self.device_transform(raw, params)
+      batch, status = self._transform_examples(examples, raw, params)
       batch['depth_scale'] = torch.from_numpy(
           np.array([e['depth_scale'] for e in examples], F32)).to(dev)
       if self.return_filename:
         batch['filename'] = [e['filename'] for e in examples]
         batch['scan_id'] = [e['scan_id'] for e in examples]
-      return batch
+      return batch, status
 
     def enqueue(futures):
       """A batch queued on the device with its inflate unchecked, or the exception that stopped it
@@ -337,7 +358,8 @@ class R2RImageDataset:
         return None
       try:
         examples = [f.result() for f in futures]
-        raw, check = png.decode_png_batch_async({k: [e[k] for e in examples] for k in RAW_DTYPES}, dev)
+        raw, check = png.decode_png_batch_async(
+            {k: [e[k] for e in examples] for k in self.RAW_DTYPES}, dev)
         return finish(examples, raw), check
       except Exception as e:   # noqa: BLE001  re-raised below
         return e
@@ -350,16 +372,198 @@ class R2RImageDataset:
           if isinstance(queued, Exception):
             raise queued
           following = enqueue(submit(pool))   # queued behind this batch, ahead of the caller's step
-          batch, check = queued
+          (batch, status), check = queued
           check.check()
+          if status is not None:
+            status.check()
           yield batch
           queued = following
         return
       while pending is not None:
         examples = [f.result() for f in pending]
         pending = submit(pool)   # inflates under the step that consumes the batch below
-        raw = png.decode_png_batch({k: [e[k] for e in examples] for k in RAW_DTYPES}, dev, threads)
-        yield finish(examples, raw)
+        raw = png.decode_png_batch({k: [e[k] for e in examples] for k in self.RAW_DTYPES}, dev,
+                                   threads)
+        batch, status = finish(examples, raw)
+        if status is not None:
+          status.check()
+        yield batch
+
+
+# RAW_DTYPES / IMAGE_PLANES of an RE10K record: `visible_mask` where `blurred_mask` stood (:232-240)
+RE10K_RAW_DTYPES = dict(image=torch.uint8, proj_image=torch.uint8, depth=torch.int16,
+                        proj_depth=torch.int16, proj_mask=torch.uint8, visible_mask=torch.uint8,
+                        segmentation=torch.uint8)
+RE10K_IMAGE_PLANES = dict(image=('image/encoded', 3, 8), proj_image=('proj/encoded', 3, 8),
+                          depth=('image/depth', 1, 16), proj_depth=('proj/depth', 1, 16),
+                          proj_mask=('proj/mask', 1, 8), visible_mask=('image/visible_mask', 1, 8),
+                          segmentation=('image/segmentation/class/encoded', 1, 8))
+RE10K_STATUS = {1: 'visible_mask has no visible pixel',
+                2: 'the crop box does not lie inside the frame'}
+
+
+class PendingCrop(Readback):
+  """The status words of one `se3ds_re10k_transform` launch on their way to the host: `check()`
+  waits for them and raises ValueError for the first example whose crop could not be made.  The
+  batch counts only once it has returned."""
+
+  def check(self) -> None:
+    words = self.wait()
+    bad = np.flatnonzero(words)
+    if bad.size:
+      i = int(bad[0])
+      reason = RE10K_STATUS.get(int(words[i]), f'status {int(words[i])}')
+      raise ValueError(f'example {i} of the batch: {reason}')
+
+
+@gin.configurable
+class RE10KImageDataset(R2RImageDataset):
+  """Preprocessing of RealEstate10K records for training: the reference's `_parse` branch for
+  DatasetType.RE10K (:232-240) and `_transform_fn_re10k` (:377-535), whose call the reference has
+  commented out (:538-546).  Here the dispatch is this class, not `dataset_type`: R2RImageDataset
+  goes on refusing such records.  Same constructor arguments, defaults and gin selectors as
+  R2RImageDataset (`re_10k_crop` is off by default, as in the reference).
+
+  With `re_10k_crop and random_crop` every plane is cropped to a padded, shifted box around the
+  visible pixels and resized to (image_size, 2 * image_size); otherwise the outputs keep the raw
+  size and hold conversion, band masks and the batch transform only (:474).  The extents of the
+  visible pixels are found on the device (`se3ds_re10k_extent`) and the box is evaluated inside
+  the gather (`se3ds_re10k_transform`, csrc/re10k_box_core.h): the host never sees the mask.
+
+  `input_fn` is R2RImageDataset's, signature and order of the records included; its batches carry
+  `bbox` as well.  The device leaves one status word per example (0 ok, 1 no visible pixel, 2 the
+  box does not lie inside the frame); input_fn reads a batch's words just before it yields the
+  batch, behind the launches of the next one with inflate='device', and raises ValueError naming
+  the example."""
+
+  RAW_DTYPES = RE10K_RAW_DTYPES
+  IMAGE_PLANES = RE10K_IMAGE_PLANES
+
+  def _parse(self, record: bytes, inflate: str = 'host') -> dict:
+    """As R2RImageDataset._parse, with the plane `visible_mask` (`image/visible_mask`, 8-bit grey,
+    frame size) in place of `blurred_mask`.  `image/blurred_mask` is not read: the reference decodes
+    it and then overwrites it with 1 - visible_mask (:238), so it may be empty here.  A record of
+    another dataset_type, and a missing or wrong-kind `image/visible_mask`, raise ValueError."""
+    ex = tf_records.apply_features(tf_records.parse_example(record), self._features())
+    if ex['dataset_type'] != DatasetType.RE10K.value:
+      raise ValueError(f"dataset_type {int(ex['dataset_type'])}: RE10KImageDataset reads records of "
+                       f'DatasetType.RE10K ({DatasetType.RE10K.value}) only')
+    return self._parsed(ex, inflate)
+
+  # ------------------------------------------------------------------------------ the draws
+  def draw_params(self, rng: np.random.Generator, height: int, width: int) -> dict:
+    """One example's random draws, in the statement order of `_transform_fn_re10k` (:389-443), each
+    rounded to fp32: hmask and vmask as in R2RImageDataset.draw_params, then, only with
+    re_10k_crop, pad in [pad_minval, pad_maxval) and x_shift, y_shift in +-0.5 |pad|.  No resize,
+    roll, flip or crop offset is drawn; the generator is not touched for a part that is off."""
+    prm = dict(hmask=None, vmask=None, pad=None, x_shift=None, y_shift=None)
+    if self.horizontal_mask_ratio > 0:
+      mask_ratio = F32(rng.uniform(0, self.horizontal_mask_ratio))
+      keep_ratio = F32(1) - mask_ratio
+      start = F32(rng.uniform(0, width))
+      end = F32(np.mod(start + F32(width) * keep_ratio, F32(width)))
+      prm['hmask'] = (2 if start > end else 1, float(start), float(end))
+    if self.vertical_mask_ratio > 0:
+      mask_ratio = F32(rng.uniform(0, self.vertical_mask_ratio))
+      image_height = F32(height) * (F32(1) - mask_ratio)
+      start = F32(rng.uniform(0, max(float(F32(height) - image_height), 1e-30)))
+      prm['vmask'] = (float(start), float(start + image_height))
+    if self.re_10k_crop:
+      pad = F32(rng.uniform(self.pad_minval, self.pad_maxval))
+      half = F32(0.5) * np.abs(pad)
+      prm['pad'] = float(pad)
+      prm['x_shift'] = float(F32(rng.uniform(-half, half)))
+      prm['y_shift'] = float(F32(rng.uniform(-half, half)))
+    return prm
+
+  # ------------------------------------------------------------------------- device transform
+  def _launch(self, raw: Dict[str, torch.Tensor], params: List[dict], bbox=None):
+    """Both launches of one batch, nothing waited for: -> (batch, PendingCrop)."""
+    for k, dt in RE10K_RAW_DTYPES.items():
+      _lib.require_cuda(raw[k])
+      if raw[k].dtype != dt:
+        raise ValueError(f'{k}: expected {dt}, got {raw[k].dtype}')
+    n, h0, w0 = raw['proj_mask'].shape
+    for k in RE10K_RAW_DTYPES:
+      if tuple(raw[k].shape[:3]) != (n, h0, w0):
+        raise ValueError(f'{k}: {tuple(raw[k].shape)}, proj_mask is {(n, h0, w0)}')
+    if len(params) != n:
+      raise ValueError(f'{len(params)} parameter rows for a batch of {n}')
+    crop = bool(self.re_10k_crop and self.random_crop)
+    h, w = (self.image_size, 2 * self.image_size) if crop else (h0, w0)
+    ext = np.tile(np.array([h0, -1, w0, -1], np.int32), (n, 1))
+    ip = np.zeros((n, 3), np.int32)
+    fp = np.zeros((n, 7), F32)
+    for i, prm in enumerate(params):
+      if prm.get('hmask') is not None:
+        if prm['hmask'][0] not in (1, 2):
+          raise ValueError(f"hmask mode {prm['hmask'][0]} (1: start < x < end, 2: x > start or x < end)")
+        ip[i, 0], fp[i, 0], fp[i, 1] = prm['hmask']
+      if prm.get('vmask') is not None:
+        ip[i, 1] = 1
+        fp[i, 2], fp[i, 3] = prm['vmask']
+      if crop:
+        if prm.get('pad') is None:
+          raise ValueError(f'parameter row {i} has no pad / x_shift / y_shift draw')
+        ip[i, 2] = 1
+        fp[i, 4:7] = (prm['pad'], prm['x_shift'], prm['y_shift'])
+    dev = raw['proj_mask'].device
+    if bbox is None:
+      if not crop:
+        raise ValueError("bbox: the record's bbox is needed unless re_10k_crop and random_crop")
+    elif not crop:
+      bbox = torch.as_tensor(bbox, dtype=torch.float32).to(dev)
+      if tuple(bbox.shape) != (n, 4):
+        raise ValueError(f'bbox: expected {(n, 4)}, got {tuple(bbox.shape)}')
+    with torch.cuda.device(dev):
+      # one upload: the initial extents, the integer rows, the fp32 rows as their bit patterns
+      rows = torch.from_numpy(np.concatenate(
+          [ext.reshape(-1), ip.reshape(-1), fp.reshape(-1).view(np.int32)])).to(dev)
+      extd, ipd, fpd = rows[:4 * n], rows[4 * n:7 * n], rows[7 * n:].view(torch.float32)
+      f = lambda c: torch.empty((n, h, w, c), dtype=torch.float32, device=dev)
+      out = dict(image=f(3), proj_image=f(3), proj_mask=f(1), proj_depth=f(1), depth=f(1),
+                 blurred_mask=f(1),
+                 segmentation=torch.empty((n, h, w, 1), dtype=torch.int32, device=dev))
+      status = torch.empty((n,), dtype=torch.int32, device=dev)
+      r = {k: raw[k].contiguous() for k in RE10K_RAW_DTYPES}
+      L = _lib.lib()
+      if crop:
+        out['bbox'] = torch.empty((n, 4), dtype=torch.int32, device=dev)
+        rc = L.se3ds_re10k_extent(_lib.ptr(r['visible_mask']), n, h0, w0, _lib.ptr(extd), _lib.stream())
+        _lib.check(rc, 'se3ds_re10k_extent')
+      else:
+        out['bbox'] = bbox
+      rc = L.se3ds_re10k_transform(
+          _lib.ptr(r['image']), _lib.ptr(r['proj_image']), _lib.ptr(r['depth']),
+          _lib.ptr(r['proj_depth']), _lib.ptr(r['proj_mask']), _lib.ptr(r['visible_mask']),
+          _lib.ptr(r['segmentation']), _lib.ptr(extd) if crop else None, _lib.ptr(ipd),
+          _lib.ptr(fpd), n, h0, w0, h, w, _lib.ptr(out['image']), _lib.ptr(out['proj_image']),
+          _lib.ptr(out['proj_mask']), _lib.ptr(out['proj_depth']), _lib.ptr(out['depth']),
+          _lib.ptr(out['blurred_mask']), _lib.ptr(out['segmentation']),
+          _lib.ptr(out['bbox']) if crop else None, _lib.ptr(status), _lib.stream())
+      _lib.check(rc, 'se3ds_re10k_transform')
+      return out, PendingCrop(status)
+
+  def device_transform(self, raw: Dict[str, torch.Tensor], params: List[dict], bbox=None
+                       ) -> Dict[str, torch.Tensor]:
+    """raw: R2RImageDataset.device_transform's dict with `visible_mask` uint8 (N,H0,W0) in place of
+    `blurred_mask`.  Returns the step's batch dict (`blurred_mask` = 1 - visible) plus `bbox`:
+      * re_10k_crop and random_crop: outputs at (image_size, 2 * image_size); bbox int32 (N,4) =
+        [x_min, y_min, x_max, y_max] as the device found it (:520);
+      * otherwise: outputs at the raw (H0, W0); bbox is the argument, the records' fp32 (N,4).
+    One small download checks the per-example status; an example without a visible pixel, or
+    whose box does not lie inside the frame, raises ValueError naming it."""
+    out, status = self._launch(raw, params, bbox)
+    status.check()
+    return out
+
+  def transform(self, raw: Dict[str, torch.Tensor], rng: np.random.Generator, bbox=None):
+    """Draws + device transform of one batch."""
+    n, h0, w0 = raw['proj_mask'].shape
+    return self.device_transform(raw, [self.draw_params(rng, h0, w0) for _ in range(n)], bbox)
+
+  def _transform_examples(self, examples, raw, params):
+    return self._launch(raw, params, np.stack([np.asarray(e['bbox'], F32) for e in examples]))
 
 
 VIDEO_PLANES = dict(segmentation=torch.uint8, pathdreamer_segmentation=torch.uint8,
