@@ -916,6 +916,54 @@ int se3ds_jpeg_encode_pack_unit_blocks(void);
 int se3ds_jpeg_encode_block_words(void);
 int se3ds_jpeg_encode_tile_blocks(void);
 
+/* Animated GIF encoding of many uint8 videos (frames x height x width x 1|3, dense): one global
+ * palette of 256 entries per video, ordered dither, LZW in independent strips packed at bit
+ * granularity.  The format is DESIGN.md 3.18; csrc/gif.hip, the LZW walk in csrc/gif_lzw_core.h.
+ * The caller runs the median cut between histogram and lut, and adds the container (utils/gif.py).
+ * table: device int64 [n][se3ds_gif_fields() = 12]: device pointer of the pixels, frames, height,
+ * width, channels (1: the pixel is the index; 3: RGB), dither amplitude 0..255, and six fields that
+ * se3ds_gif_plan(host_table, n) fills in the HOST copy before it is uploaded: frames and strips of
+ * the videos in front, the byte offsets of the video's index plane, strip slots and output area,
+ * and the bytes of one frame's output area (its sub-blocks at their longest, rounded up to 16).
+ * host_table: the HOST copy, validated before anything runs (BADSHAPE: n < 1 or > 65535, a null
+ * pointer, frames < 1, a size outside 1..65535, channels outside {1, 3}, dither outside 0..255, a
+ * derived field that is not what se3ds_gif_plan writes, an out buffer that is too small or
+ * misaligned; UNSUPPORTED: more than 2^31 - 1 frames or strips; WORKSPACE: a workspace that is too
+ * small).  workspace: device, 16-byte aligned, se3ds_gif_workspace_bytes(host_table, n) bytes (0:
+ * the table is not valid); its regions begin at se3ds_gif_workspace_offset(host_table, n, region):
+ * 0 = histograms uint32 [n][32768], 1 = look-up tables uint8 [n][32768], 2 = index planes, 3 =
+ * strip slots, 4 = strip bit counts uint32, 5 = strip bit positions uint64, 6 = the end.
+ * A strip is ceil(se3ds_gif_strip_pixels() / width) whole rows of a frame; its slot has
+ * se3ds_gif_strip_slot_bytes(pixels of a full strip) bytes.
+ * Stages, each one call on `stream` without a host synchronisation, each reading what the one before
+ * left in the workspace:
+ *   histogram  colour videos: bin = (r>>3)<<10 | (g>>3)<<5 | (b>>3) over every pixel, exact in 32 bits.
+ *   lut        palettes: device uint8 [n][256][3]; used: device int32 [n], the entries in use, 0 = a
+ *              grey video.  The used entry nearest every bin centre, lowest index on a tie.
+ *   index      dither, clamp, look-up: one byte per pixel of every colour video.
+ *   lzw        one wave per strip -> the strip's code stream in its slot, and its bit count.
+ *   pack       out: device, 8-byte aligned, se3ds_gif_out_bytes(host_table, n) bytes: int64 [frames]
+ *              (rounded up to 16 bytes) with every frame's byte count, then per frame, at the video's
+ *              output offset + frame * its frame bytes, the sub-blocks and the terminator.
+ * Integer arithmetic throughout: the same bytes on every run. */
+int se3ds_gif_plan(int64_t* host_table, int n);
+size_t se3ds_gif_workspace_bytes(const int64_t* host_table, int n);
+int64_t se3ds_gif_out_bytes(const int64_t* host_table, int n);
+int64_t se3ds_gif_workspace_offset(const int64_t* host_table, int n, int region);
+int se3ds_gif_fields(void);
+int se3ds_gif_strip_pixels(void);
+int64_t se3ds_gif_strip_slot_bytes(int64_t pixels);
+int se3ds_gif_histogram(const int64_t* table, const int64_t* host_table, int n, uint8_t* workspace,
+                        int64_t workspace_bytes, void* stream);
+int se3ds_gif_lut(const int64_t* table, const int64_t* host_table, int n, const uint8_t* palettes,
+                  const int32_t* used, uint8_t* workspace, int64_t workspace_bytes, void* stream);
+int se3ds_gif_index(const int64_t* table, const int64_t* host_table, int n, uint8_t* workspace,
+                    int64_t workspace_bytes, void* stream);
+int se3ds_gif_lzw(const int64_t* table, const int64_t* host_table, int n, uint8_t* workspace,
+                  int64_t workspace_bytes, void* stream);
+int se3ds_gif_pack(const int64_t* table, const int64_t* host_table, int n, uint8_t* workspace,
+                   int64_t workspace_bytes, uint8_t* out, int64_t out_bytes, void* stream);
+
 /* ======================================================================================
  * Writing training records -- the inverse of datasets/indoor_datasets.py:125-247.
  * csrc/records.hip, datasets/record_writer.py.

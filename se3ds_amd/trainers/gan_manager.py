@@ -538,9 +538,33 @@ class GANManager(abc.ABC):
       writer.writerow(row)
     return row
 
-  def _save_rollout_images(self, rollout, step):
-    """images/<split>/<step>/<frame>/<example>_{rgb,depth}.png of the EMA roll-out (:274-296)."""
+  @staticmethod
+  def _rollout_videos(rollout):
+    """The roll-out's frames as the PNGs hold them -- x * 255.5, truncated, saturated -- stacked over
+    the frame index: (rgb, depth), uint8 device tensors (N,T,H,W,3) and (N,T,H,W,1)."""
+    from se3ds_amd.models.models import _quantize
+    return tuple(
+        torch.stack([_quantize(f.detach().float(), torch.uint8, mul=255.5, div=1.0, lo=0.0, hi=255.0)
+                     for f in frames], dim=1)
+        for frames in (rollout.generated, rollout.pred_depth))
+
+  def _save_rollout_images(self, rollout, step, video: bool = False, fps: float = 10):
+    """images/<split>/<step>/<frame>/<example>_{rgb,depth}.png of the EMA roll-out (:274-296).
+    video: also images/<split>/<step>/<example>_{rgb,depth}.gif, the same pixels as animated GIFs
+    (depth lossless, rgb through an adaptive palette), all examples encoded in one batch on the
+    device (utils/gif.encode_gif_batch)."""
     root = os.path.join(self.model_dir, 'images', self.test_split, str(step))
+    if video:
+      from se3ds_amd.utils import gif
+      os.makedirs(root, exist_ok=True)
+      paths, videos = [], []
+      for suffix, stacked in zip(('rgb', 'depth'), self._rollout_videos(rollout)):
+        for example_idx in range(stacked.shape[0]):
+          paths.append(os.path.join(root, f'{example_idx}_{suffix}.gif'))
+          videos.append(stacked[example_idx])
+      for path, data in zip(paths, gif.encode_gif_batch(videos, fps=fps)):
+        with open(path, 'wb') as f:
+          f.write(data)
     if self.png_encoder not in ('host', 'device'):
       raise ValueError(f"png_encoder: 'host' or 'device', got {self.png_encoder!r}")
     if self.png_encoder == 'device':
@@ -571,7 +595,7 @@ class GANManager(abc.ABC):
             f.write(_encode_png(pixels[example_idx]))
 
   def test(self, eval_examples=None, checkpoints=None, unit_test: bool = False, inception=None,
-           logger=None, frechet: str = 'host'):
+           logger=None, frechet: str = 'host', rollout_video: bool = False):
     """The evaluation loop of the reference (:233-322) minus the polling task manager.  logger: a
     utils/logger.UniversalLogger; per checkpoint the row's values go to it as scalars and the nine
     image grids of the display batch's roll-out under the prefix test_split (:241,320-321).  eval_examples: parsed trajectory examples (what R2RVideoDataset.input_fn takes: a
@@ -583,7 +607,10 @@ class GANManager(abc.ABC):
     Per checkpoint: restore, roll the display batch out (_get_image_grid), write the EMA
     roll-out's frames as PNG, FID / RMSE per frame index for the generator and its EMA, one CSV
     row.  The step of a row (and of its image directory) is the number that ends the checkpoint's
-    name.  frechet: EvalMetric's Frechet method, 'host' or 'device'.  Returns the rows written."""
+    name.  frechet: EvalMetric's Frechet method, 'host' or 'device'.  rollout_video: also write the
+    EMA roll-out of every example as <example>_rgb.gif and <example>_depth.gif next to the frame
+    directories and, with a logger, log the generated and the EMA roll-out as videos
+    (<split>_raw_generated_video, <split>_ema_generated_video).  Returns the rows written."""
     from se3ds_amd.datasets import indoor_datasets
     from se3ds_amd.utils import eval_metric
     if self.strategy.num_replicas_in_sync != 1:
@@ -616,7 +643,7 @@ class GANManager(abc.ABC):
         self.restore_checkpoint(checkpoint_path)
       rollouts = self._get_image_grid(self.display_batch,
                                       modes=('ema',) if logger is None else ('normal', 'ema'))
-      self._save_rollout_images(rollouts['ema'], step)
+      self._save_rollout_images(rollouts['ema'], step, video=rollout_video)
       fid, _, rmse = metric.calculate_fid_score(self.generator)
       ema_fid, _, ema_rmse = metric.calculate_fid_score(self.ema_generator)
       result = {}
@@ -628,6 +655,12 @@ class GANManager(abc.ABC):
         logger.log_scalars(step, **{k: float(rows[-1][k]) for k in result})   # as the row has them
         image_dict, _ = self._get_image_dict(rollouts, self.display_batch, self.test_split)
         logger.log_images(step, **image_dict)
+        if rollout_video:
+          videos = {f'{self.test_split}_{name}_generated_video': self._rollout_videos(rollouts[mode])[0]
+                    for name, mode in (('raw', 'normal'), ('ema', 'ema'))}
+          if logger.encoder == 'host':
+            videos = {k: v.cpu().numpy() for k, v in videos.items()}
+          logger.log_videos(step, **videos)
     return rows
 
   # -------------------------------------------------------------------------- checkpoint

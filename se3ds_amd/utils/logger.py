@@ -1,13 +1,14 @@
 """The reference's utils/logger.UniversalLogger without TensorFlow: scalars and image grids go to
 a TensorBoard event file (utils/tf_events.py) and, for scalars, to the log.  Images are PNG-encoded
 on the device in one batch per call (utils/png.encode_png_batch), or on the host for NumPy arrays;
-image_format='jpeg' writes baseline JPEG instead (utils/jpeg.encode_jpeg_batch, device only)."""
+image_format='jpeg' writes baseline JPEG instead (utils/jpeg.encode_jpeg_batch, device only).
+Videos go out as animated GIFs in image summaries (utils/gif.py), on the device or on the host."""
 import logging
 from typing import Callable, Optional
 
 import numpy as np
 
-from se3ds_amd.utils import jpeg, png, tf_events
+from se3ds_amd.utils import gif, jpeg, png, tf_events
 
 
 class UniversalLogger:
@@ -67,6 +68,33 @@ class UniversalLogger:
     for tag, x, data in zip(tags, images, files):
       self.summary_writer.add_image(tag, data, int(x.shape[0]), int(x.shape[1]), step,
                                     channels=int(x.shape[2]))
+    self.summary_writer.flush()
+
+  def log_videos(self, step: int, fps: float = 10, max_outputs: int = 3, **kwargs):
+    """Log videos (given as keyword arguments): each value uint8 (k,T,H,W,C), C 1 or 3.  The first
+    min(k, max_outputs) go out as animated GIFs at `fps` under the tag `name` (k = 1) or
+    `name/video/<i>`, in an image summary, which is how TensorBoard's image dashboard plays them;
+    all videos of the call are encoded in one batch (utils/gif.encode_gif_batch, or encode_gif_host
+    for the NumPy arrays of encoder='host')."""
+    tags, videos = [], []
+    for name, value in sorted(kwargs.items()):
+      if len(value.shape) != 5 or value.shape[4] not in (1, 3):
+        raise ValueError(f'{name}: uint8 (k,T,H,W,1|3) expected, got {tuple(value.shape)}')
+      if (self.encoder == 'host') != isinstance(value, np.ndarray):
+        raise ValueError(f"{name}: encoder='host' takes NumPy arrays, encoder='device' device tensors")
+      count = min(int(value.shape[0]), int(max_outputs))
+      for i in range(count):
+        tags.append(name if value.shape[0] == 1 else f'{name}/video/{i}')
+        videos.append(value[i])
+    if not videos:
+      return
+    if self.encoder == 'device':
+      files = gif.encode_gif_batch(videos, fps=fps)
+    else:
+      files = [gif.encode_gif_host(x, fps=fps) for x in videos]
+    for tag, x, data in zip(tags, videos, files):
+      self.summary_writer.add_image(tag, data, int(x.shape[1]), int(x.shape[2]), step,
+                                    channels=int(x.shape[3]))
     self.summary_writer.flush()
 
   def close(self):
