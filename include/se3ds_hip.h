@@ -1252,6 +1252,55 @@ int64_t se3ds_ply_max_points(void);
 int se3ds_ply_binary(const float* coords, int64_t row_stride, const void* rgb, int rgb_dtype,
                      int64_t m, uint8_t* out, int64_t out_capacity, int32_t* flag, void* stream);
 
+/* ======================================================================================
+ * Paired image metrics -- utils/image_metrics.py: PSNR, SSIM and MS-SSIM as tf.image.psnr /
+ * ssim / ssim_multiscale define them (not in the reference tree).  csrc/image_metrics.hip.
+ * ====================================================================================== */
+
+/* SSIM of a against b, both (n, h, w, c) NHWC dense, both SE3DS_F32 or both SE3DS_U8, c in 1..4.
+ * weights: HOST pointer to filter_size fp32 taps (1..15), copied into the launch.  G is the
+ * separable window sum over a VALID window: the horizontal pass, then the vertical pass over its
+ * results, taps in ascending order, the first tap one product and every later tap one product and
+ * one add, all in binary64 with the taps and the pixels widened exactly; a b and a a + b b are formed
+ * in binary64 before the window.  With c1 = (k1 max_val)^2, c2 = (k2 max_val)^2, m0 = G(a), m1 = G(b):
+ *   n0 = 2 m0 m1, d0 = m0 m0 + m1 m1, lum = (n0 + c1) / (d0 + c1)
+ *   n1 = 2 G(a b), d1 = G(a a + b b),  cs = (n1 - n0 + c2) / (d1 - d0 + c2)
+ * per pixel of the (h - filter_size + 1) x (w - filter_size + 1) map and per channel.
+ * ssim_mean, cs_mean: device binary64 (n, c), the means of lum cs and of cs over the map.  map: NULL,
+ * or device binary64 (n, h', w', c) that receives lum cs.  workspace: device, 8-byte aligned,
+ * se3ds_ssim_workspace_bytes(n, h, w, c, filter_size) bytes (0: the shape is not valid).
+ * Two launches on `stream`: a workgroup per se3ds_ssim_tile_rows() x se3ds_ssim_tile_cols() tile of
+ * the map stages its pixels (with a halo of filter_size - 1) in LDS once, forms all window sums there
+ * and writes its sums to the workspace; the second launch adds an image's records in a fixed order.
+ * No filtered plane is written, no atomics, no host synchronisation: deterministic bits.
+ * All checks run before the first HIP call.  BADSHAPE: n outside 1..65535, c outside 1..4,
+ * filter_size outside 1..15, h or w < filter_size or > 32768, max_val not > 0, a null or misaligned
+ * pointer (map may be null); BADDTYPE; WORKSPACE: too small. */
+int se3ds_ssim(const void* a, const void* b, int dtype, int n, int h, int w, int c,
+               const float* weights, int filter_size, double max_val, double k1, double k2,
+               double* ssim_mean, double* cs_mean, double* map, void* workspace,
+               size_t workspace_bytes, void* stream);
+size_t se3ds_ssim_workspace_bytes(int n, int h, int w, int c, int filter_size);
+int se3ds_ssim_tile_rows(void);
+int se3ds_ssim_tile_cols(void);
+/* out[i] = sum over image i of (a - b)^2, device binary64 (n): a, b (n, elems_per_image) dense, both
+ * F32 or both U8.  F32: ((double)a - (double)b)^2 added in binary64; U8: integers, the sum is exact.
+ * Two stages as above: a workgroup per se3ds_sqdiff_chunk() elements, then a fixed-order sum; no
+ * atomics.  workspace: device, 8-byte aligned, se3ds_sqdiff_workspace_bytes(n, elems_per_image) bytes
+ * (0: not valid).  BADSHAPE: n outside 1..65535, elems_per_image outside 1..2^40, n * chunks >
+ * INT32_MAX, a null or misaligned pointer; BADDTYPE; WORKSPACE. */
+int se3ds_sqdiff_sum(const void* a, const void* b, int dtype, int n, int64_t elems_per_image,
+                     double* out, void* workspace, size_t workspace_bytes, void* stream);
+size_t se3ds_sqdiff_workspace_bytes(int n, int64_t elems_per_image);
+int se3ds_sqdiff_chunk(void);
+/* The step between MS-SSIM scales: x (n, h, w, c) F32 or U8 -> out fp32 (n, ceil(h / 2), ceil(w / 2),
+ * c), the 2 x 2 mean at stride 2 after an odd side is extended by repeating its last row or column
+ * (TensorFlow's SYMMETRIC pad of one): ((x00 + x01) + x10) + x11 in binary64, times 0.25, rounded
+ * once to fp32.  One launch.  BADSHAPE: n outside 1..65535, h or w outside 1..32768, c outside 1..4,
+ * a null or misaligned pointer; BADDTYPE. */
+int se3ds_downsample2_sym(const void* x, int dtype, int n, int h, int w, int c, float* out,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,7 @@ PER_FILE = {
     'frechet.hip': ['-ffp-contract=off'],    # the reductions and epilogues round as written
     'semantic.hip': ['-ffp-contract=off'],   # the metric sums round every term as written
     'gif.hip': ['-ffp-contract=off'],        # integer only; kept with the exact files
+    'image_metrics.hip': ['-ffp-contract=off'],   # binary64 window sums: a product, then an add
 }
 
 

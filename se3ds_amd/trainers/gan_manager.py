@@ -595,7 +595,8 @@ class GANManager(abc.ABC):
             f.write(_encode_png(pixels[example_idx]))
 
   def test(self, eval_examples=None, checkpoints=None, unit_test: bool = False, inception=None,
-           logger=None, frechet: str = 'host', rollout_video: bool = False):
+           logger=None, frechet: str = 'host', rollout_video: bool = False,
+           image_metrics: bool = False):
     """The evaluation loop of the reference (:233-322) minus the polling task manager.  logger: a
     utils/logger.UniversalLogger; per checkpoint the row's values go to it as scalars and the nine
     image grids of the display batch's roll-out under the prefix test_split (:241,320-321).  eval_examples: parsed trajectory examples (what R2RVideoDataset.input_fn takes: a
@@ -610,7 +611,10 @@ class GANManager(abc.ABC):
     name.  frechet: EvalMetric's Frechet method, 'host' or 'device'.  rollout_video: also write the
     EMA roll-out of every example as <example>_rgb.gif and <example>_depth.gif next to the frame
     directories and, with a logger, log the generated and the EMA roll-out as videos
-    (<split>_raw_generated_video, <split>_ema_generated_video).  Returns the rows written."""
+    (<split>_raw_generated_video, <split>_ema_generated_video).  image_metrics: the row (and the
+    logger's scalars) also get <split>/eval_image/{psnr,ema_psnr,ssim,ema_ssim}@<i>, the PSNR and SSIM
+    of every generated frame against its ground-truth frame (EvalMetric.image_scores); a score file
+    written without them has other columns and is refused.  Returns the rows written."""
     from se3ds_amd.datasets import indoor_datasets
     from se3ds_amd.utils import eval_metric
     if self.strategy.num_replicas_in_sync != 1:
@@ -634,7 +638,7 @@ class GANManager(abc.ABC):
     metric = eval_metric.EvalMetric(ds=self.eval_ds, eval_num=self.eval_size or self.eval_num,
                                     batch_size=self.test_batch_size, strategy=None, avg_num=1,
                                     eval_seq_len=self.eval_seq_len, inception=inception,
-                                    frechet=frechet)
+                                    frechet=frechet, image_metrics=image_metrics)
     if not hasattr(self, 'generator'):
       self._create_obj()
     rows = []
@@ -645,10 +649,15 @@ class GANManager(abc.ABC):
                                       modes=('ema',) if logger is None else ('normal', 'ema'))
       self._save_rollout_images(rollouts['ema'], step, video=rollout_video)
       fid, _, rmse = metric.calculate_fid_score(self.generator)
+      scores = metric.image_scores
       ema_fid, _, ema_rmse = metric.calculate_fid_score(self.ema_generator)
+      columns = [('fid', fid), ('ema_fid', ema_fid), ('rmse', rmse), ('ema_rmse', ema_rmse)]
+      if image_metrics:
+        columns += [('psnr', scores['psnr']), ('ema_psnr', metric.image_scores['psnr']),
+                    ('ssim', scores['ssim']), ('ema_ssim', metric.image_scores['ssim'])]
       result = {}
       for i in fid:
-        for k, v in (('fid', fid), ('ema_fid', ema_fid), ('rmse', rmse), ('ema_rmse', ema_rmse)):
+        for k, v in columns:
           result[f'{self.test_split}/eval_image/{k}@{i}'] = v[i]
       rows.append(self._add_eval_result(checkpoint_path, step, result))
       if logger is not None:

@@ -12,7 +12,7 @@ generated frames go through the augment + crop + resize gather and Inception-v3 
 (utils/inception_utils.py); their 2048-d pools are reduced there into binary64 moments
 (FeatureMoments), so only the mean and covariance reach the host for the Frechet distance -- or, with
 frechet='device', nothing but the distance does (inception_utils.frechet_distance_device)."""
-from typing import Callable, Dict, Iterator, List, NamedTuple, Optional
+from typing import Callable, Dict, Iterator, List, NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -21,6 +21,7 @@ from se3ds_amd import _lib
 from se3ds_amd import constants
 from se3ds_amd.datasets import indoor_datasets
 from se3ds_amd.models.models import _quantize
+from se3ds_amd.utils import image_metrics as image_metrics_lib
 from se3ds_amd.utils import inception_utils
 from se3ds_amd.utils import pano_utils
 from se3ds_amd.utils import point_cloud_utils
@@ -35,6 +36,8 @@ class RolloutOutput(NamedTuple):
   proj_depth: List[torch.Tensor]    # per frame (N,H,W,1)
   depth_rmse: List[torch.Tensor]    # per frame (N,) (eval_metric.py:225-234)
   memory: PointCloudMemory
+  psnr: Sequence[torch.Tensor] = ()   # image_metrics=True: per frame (N,) float64, generated[k] against
+  ssim: Sequence[torch.Tensor] = ()   # image[:, k] at max_val 1 (utils/image_metrics.py); else empty
 
 
 def depth_rmse(depth: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
@@ -57,12 +60,14 @@ def depth_rmse(depth: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
 
 def generated_rollout(generator_fn: Callable, inputs: Dict[str, torch.Tensor], eval_seq_len: int,
                       predict_depth: bool = True,
-                      unproject_void_class: float = constants.INVALID_RGB_VALUE) -> RolloutOutput:
+                      unproject_void_class: float = constants.INVALID_RGB_VALUE,
+                      image_metrics: bool = False) -> RolloutOutput:
   """inputs: image (N,T,H,W,3) fp32 [0,1], depth (N,T,H,W,1), position (N,T,3), depth_scale (N,).
   generator_fn(inputs=[cond, None], training=False) -> [mu, logvar, kld, depth, seg, depth_seg,
   rgb].  `unproject_void_class`: eval_metric.py:236-238 passes INVALID_RGB_VALUE, gan_manager.py:
   536-539 passes 0 -- both are kept.  predict_depth=False feeds the ground-truth depth of every
-  frame (gan_manager.py:468-469)."""
+  frame (gan_manager.py:468-469).  image_metrics=True also scores every generated frame against its
+  ground-truth frame: out.psnr[k], out.ssim[k] (N,) float64 (not in the reference)."""
   image, depth, position = inputs['image'], inputs['depth'], inputs['position']
   _lib.require_cuda(image, depth, position)
   n, t, h, w, _ = image.shape
@@ -71,7 +76,7 @@ def generated_rollout(generator_fn: Callable, inputs: Dict[str, torch.Tensor], e
   depth_scale = float(inputs['depth_scale'][0])   # all depth_scale within a batch are the same
   dev = image.device
   memory = PointCloudMemory(n, 3, torch.int32, dev, capacity=eval_seq_len * h * w)
-  out = RolloutOutput([], [], [], [], [], [], memory)
+  out = RolloutOutput([], [], [], [], [], [], memory, [], [])
   prev_rgb = None
   for k in range(eval_seq_len):
     target_depth = depth[:, k].contiguous()
@@ -109,6 +114,10 @@ def generated_rollout(generator_fn: Callable, inputs: Dict[str, torch.Tensor], e
     memory.append_equirect(pc_rgb, depth_tensor[..., 0], unproject_void_class, depth_scale,
                            position=pos)
     out.generated.append(generated)
+    if image_metrics:
+      frame = generated.to(torch.float32)
+      out.psnr.append(image_metrics_lib.psnr(frame, rgb, 1.0))
+      out.ssim.append(image_metrics_lib.ssim(frame, rgb, 1.0))
     out.pred_depth.append(depth_tensor)
     out.projected.append(pred_rgb)
     out.proj_mask.append(pred_mask[..., None])
@@ -128,17 +137,21 @@ class EvalMetric:
   FeatureMoments can be merged by the caller.  keep_pools: also keep the host copies of the pools
   of the real set and of the last repeat (tests).  frechet: 'host' (NumPy / SciPy sqrtm, the
   reference's formulation) or 'device' (FeatureMoments.fid(method='device'): the real set's matrix
-  square root is computed once per frame index and reused for every generator and repeat)."""
+  square root is computed once per frame index and reused for every generator and repeat).
+  image_metrics: calculate_fid_score also averages the PSNR and SSIM of every generated frame against
+  its ground-truth frame into self.image_scores (utils/image_metrics.py; not in the reference)."""
 
   def __init__(self, ds: Iterator, eval_num: int, batch_size: int, strategy=None, avg_num: int = 3,
                num_splits: int = 1, eval_seq_len: int = 5,
                inception: Optional[inception_utils.InceptionV3] = None, seed: int = 0,
-               keep_pools: bool = False, frechet: str = 'host') -> None:
+               keep_pools: bool = False, frechet: str = 'host', image_metrics: bool = False) -> None:
     if strategy is not None:
       raise NotImplementedError('EvalMetric runs on one device; merge FeatureMoments across ranks')
     if frechet not in inception_utils.FRECHET_METHODS:
       raise ValueError(f'unknown Frechet method {frechet!r}: one of {inception_utils.FRECHET_METHODS}')
     self.frechet = frechet
+    self.image_metrics = image_metrics
+    self.image_scores = None
     self.ds = ds
     self.eval_num = eval_num
     self.batch_size = batch_size
@@ -167,17 +180,19 @@ class EvalMetric:
     pools, _ = self._inception_model(x)
     return pools
 
-  def _moments(self, frames_fn, keep_attr, rmse=None):
+  def _moments(self, frames_fn, keep_attr, rows=None):
     """Per frame index 1..T-1: FeatureMoments over the first eval_num rows of
-    (eval_num // batch_size + 1) batches (:269-315)."""
+    (eval_num // batch_size + 1) batches (:269-315).  frames_fn(batch) -> (frames, scores): scores is
+    None or {name: {i: (N,) tensor}}, per-row values of the same rows; `rows` receives them as
+    {name: {i: host array}}."""
     stats = {i: inception_utils.FeatureMoments(device=self._inception_model.device)
              for i in range(1, self.eval_seq_len)}
     kept = {i: [] for i in stats}
-    rmse_rows = {i: [] for i in stats}
+    score_rows = {}
     left = self.eval_num
     for _ in range(self.eval_num // self.batch_size + 1):
       batch = next(self.ds)
-      frames, depth_rmse_k = frames_fn(batch)
+      frames, scores = frames_fn(batch)
       if left <= 0:
         continue   # (the reference draws the batch and drops it)
       for i in stats:
@@ -185,35 +200,48 @@ class EvalMetric:
         stats[i].update(pools)
         if self.keep_pools:
           kept[i].append(pools.cpu().numpy())
-        if depth_rmse_k is not None:
-          rmse_rows[i].append(depth_rmse_k[i][:left].cpu().numpy())
+        for name, per_frame in (scores or {}).items():
+          score_rows.setdefault(name, {k: [] for k in stats})[i].append(per_frame[i][:left].cpu().numpy())
       left -= min(left, frames[1].shape[0])
     if self.keep_pools:
       setattr(self, keep_attr, {i: np.concatenate(v) for i, v in kept.items()})
-    if rmse is not None:
-      rmse.update({i: np.concatenate(v) for i, v in rmse_rows.items()})
+    if rows is not None:
+      rows.update({name: {i: np.concatenate(v) for i, v in per_frame.items()}
+                   for name, per_frame in score_rows.items()})
     return stats
 
   def calculate_fid_score(self, generator_fn: Callable):
-    """(fid, fid_std, rmse): dicts keyed by frame index 1..T-1 (:317-343)."""
-    def frames_fn(batch):
-      out = generated_rollout(generator_fn, batch, self.eval_seq_len)
-      return ({i: out.generated[i] for i in range(1, self.eval_seq_len)},
-              {i: out.depth_rmse[i] for i in range(1, self.eval_seq_len)})
+    """(fid, fid_std, rmse): dicts keyed by frame index 1..T-1 (:317-343).  With image_metrics the
+    call also sets self.image_scores = {'psnr': {i: ...}, 'ssim': {i: ...}}, averaged over the rows
+    and the repeats exactly as rmse is."""
+    indices = range(1, self.eval_seq_len)
 
-    fid_list = {i: [] for i in range(1, self.eval_seq_len)}
-    rmse_list = {i: [] for i in range(1, self.eval_seq_len)}
+    def frames_fn(batch):
+      out = generated_rollout(generator_fn, batch, self.eval_seq_len, image_metrics=self.image_metrics)
+      scores = {'rmse': {i: out.depth_rmse[i] for i in indices}}
+      if self.image_metrics:
+        scores['psnr'] = {i: out.psnr[i] for i in indices}
+        scores['ssim'] = {i: out.ssim[i] for i in indices}
+      return {i: out.generated[i] for i in indices}, scores
+
+    fid_list = {i: [] for i in indices}
+    score_list = {name: {i: [] for i in indices}
+                  for name in (('rmse', 'psnr', 'ssim') if self.image_metrics else ('rmse',))}
     for _ in range(self.avg_num):
-      rmse_total = {}
-      gen = self._moments(frames_fn, 'generated_pools', rmse=rmse_total)
+      totals = {}
+      gen = self._moments(frames_fn, 'generated_pools', rows=totals)
       for i in fid_list:
         if self.frechet == 'host':
           fid_list[i].append(gen[i].fid(self._real[i]))
         else:   # the real set owns the cached root; the trace term is symmetric in the two sets
           fid_list[i].append(self._real[i].fid(gen[i], method=self.frechet))
-        rmse_list[i].append(np.mean(rmse_total[i]))
+        for name in score_list:
+          score_list[name][i].append(np.mean(totals[name][i]))
     self.fid_list = fid_list
     fid = {k: np.mean(v) for k, v in fid_list.items()}
     fid_std = {k: np.std(v) for k, v in fid_list.items()}
-    rmse = {k: np.mean(v) for k, v in rmse_list.items()}
+    means = {name: {k: np.mean(v) for k, v in per_frame.items()} for name, per_frame in score_list.items()}
+    rmse = means.pop('rmse')
+    if self.image_metrics:
+      self.image_scores = means
     return fid, fid_std, rmse
